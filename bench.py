@@ -10,13 +10,21 @@ global message indices and detect needs no collective.
   strong scaling:          --total-messages T split over the N GPUs (T = 524,288: configs[3]'s
                            1/2/4/8-GPU curve; T = 2^20: configs[4])
 
-After the timed detect steps, one end-to-end pass (omr_dist.encode_and_reduce, the code path the
-gloo test drives) runs on the last pertinency vector: encode_pertinent_indices +
-encode_pertinent_payloads over each rank's shard with global indices, one RCCL reduce of the
-partial digests to rank 0, and the client-side retrieval (the library's Retriever) must recover
-exactly the pertinent indices and their payloads ("e2e"; --no-e2e skips it).
+A plain run sets up, warms up, times the K detect steps and prints the result line (the headline
+messages/s, ms_per_step and the stage times the timed steps recorded themselves). --dump-outputs
+DIR also writes what the last timed step computed. Everything else is behind --full:
+
+  * the DetectTimeInfo split (one pass in timing mode 2), the exactness certificate (one guarded
+    pass), the client-side decryption spot check ("correct"), the single-message latencies, the
+    rooflines / HBM / FP64 fractions and the CPU baseline;
+  * one end-to-end pass (omr_dist.encode_and_reduce, the code path the gloo test drives) on the
+    last pertinency vector: encode_pertinent_indices + encode_pertinent_payloads over each rank's
+    shard with global indices, one RCCL reduce of the partial digests to rank 0, and the
+    client-side retrieval (the library's Retriever) must recover exactly the pertinent indices and
+    their payloads ("e2e"; --no-e2e skips it).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--messages D | --total-messages T]
+                    [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -87,6 +95,14 @@ FIXED_FLOP_PER_MSG = {
 PUBLISHED_CPU_MS_PER_MSG = 234.073003  # README.md:122, 1 thread, AVX-512 CPU (model not stated)
 WEIGHT_SEED = bytes(range(1, 33))
 INDEX_SEED = 9
+# --dump-outputs: at most this many messages of the pertinency vector (32 KiB each as float64), the
+# rows a fixed seed picks; 1,024 rows are 32 MiB
+DUMP_ROWS = 1024
+DUMP_SEED = 20251
+# result-line fields a plain run leaves out (they need passes, files or checks of their own: --full)
+FULL_ONLY_KEYS = ("latency_ms_per_message", "latency_ms_per_message_throughput_kernels", "detect_fp64",
+                  "detect_time_info", "detect_bytes_per_message", "roofline", "roofline_other_rotation", "hbm",
+                  "correct", "exactness", "e2e")
 
 
 def parse():
@@ -111,9 +127,16 @@ def parse():
     ap.add_argument("--dist-timeout", type=float, default=120.0,
                     help="seconds before a collective or the rendezvous fails (N > 1): a stuck rank ends the "
                          "run with a non-zero exit instead of a hang")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the encode + reduce + retrieval pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's pertinency vector (a fixed seeded sample "
+                         "of its messages when it is larger) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the "
+                         "timing-mode-2 split, the exactness certificate, the decryption check, the end-to-end "
+                         "pass, the single-message latencies, the rooflines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the single-message latencies")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the encode + reduce + retrieval pass")
     return ap.parse_args()
 
 
@@ -202,6 +225,25 @@ def synthetic_payloads(first: int, count: int) -> np.ndarray:
     h = i * np.uint64(0x9E3779B97F4A7C15) + b * np.uint64(0xBF58476D1CE4E5B9)
     h ^= h >> np.uint64(31)
     return ((h >> np.uint64(24)) & np.uint64(255)).astype(np.uint16)
+
+
+def dump_outputs(path, d_out, rank, world):
+    """What a caller of the timed path receives from its last step: the pertinency vector (NttRlwe
+    ciphertexts, [D][2][2048] residues mod Q2 < 2^50, so float64 holds them exactly). Rows of a fixed
+    seeded sample when D > DUMP_ROWS; `pertinency_rows` are their indices within this rank's shard.
+    Rank r > 0 of a multi-GPU job writes <name>_rank<r>.npy."""
+    import torch
+
+    D = d_out.shape[0]
+    rows = np.arange(D) if D <= DUMP_ROWS else np.sort(
+        np.random.default_rng(DUMP_SEED).choice(D, DUMP_ROWS, replace=False))
+    sample = d_out[torch.from_numpy(rows.astype(np.int64)).to(d_out.device)].cpu().numpy()
+    if int(np.abs(sample).max(initial=0)) >= 1 << 53:
+        raise RuntimeError("--dump-outputs: a residue does not fit float64 exactly")
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 and rank else ""
+    np.save(os.path.join(path, f"pertinency{tag}.npy"), sample.astype(np.float64))
+    np.save(os.path.join(path, f"pertinency_rows{tag}.npy"), rows.astype(np.float64))
 
 
 def rooflines(role, dom, launches, per_launch_msgs, launch_ms_total, value, world, names):
@@ -416,108 +458,112 @@ def main():
         rank_elapsed = [float(v) for v in tt.tolist()]
         elapsed = max(rank_elapsed)
 
-    # Detector::detect_with_time_info's split (detector.rs:169-221) on one untimed pass: timing
-    # mode 2 runs the level-2 rotation and the trace as two launches, so the trace gets its own time
-    det.enable_timing(2)
-    backend.detect(d_ca, d_cb, out=d_out)
-    split = det.last_timing()
-    det.enable_timing(0)
-    backend.synchronize()
-    time_info = {"total_detect_ms": round(split["total_ms"], 2),
-                 "first_level_bootstrapping_ms": round(split["first_level_ms"], 2),
-                 "second_level_bootstrapping_ms": round(split["second_level_ms"], 2),
-                 "trace_ms": round(split["trace_ms"], 2),
-                 "key_switch_ms": round(split["key_switch_ms"], 2), "messages": int(split["messages"]),
-                 "trace_separate": bool(split["trace_separate"]),
-                 "note": "one untimed detect pass in timing mode 2 (trace as its own launch); DetectTimeInfo "
-                         "fields (detector.rs:51-57), first level includes the key switch"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, rank, world)
 
-    # Exactness certificate of the FFT external products on this run's clues: one
-    # untimed pass through the guarded kernels records the largest |y - rint(y)| of every rounded
-    # coefficient; with the key's a priori bound E the run is exact when margin < 1 - E. The pass runs
-    # in slices of at most one launch (--batch), each compared with the timed output: the extra
-    # device memory is one slice whatever D is.
-    det.rounding_margin(reset=True)
-    det.set_rounding_guard(True)
-    G = min(D, args.batch)
-    g_out = torch.empty((G, 2, 2048), dtype=torch.int64, device=dev)
-    identical = True
-    guarded_ms = 0.0
-    for s0 in range(0, D, G):
-        n = min(G, D - s0)
-        torch.cuda.synchronize(dev)
-        tg = time.perf_counter()
-        det.detect_batch_device(d_ca[s0:].data_ptr(), d_cb[s0:].data_ptr(), n, g_out.data_ptr(), stream.cuda_stream)
-        torch.cuda.synchronize(dev)
-        guarded_ms += (time.perf_counter() - tg) * 1e3
-        identical &= bool(torch.equal(g_out[:n], d_out[s0:s0 + n]))
-    det.set_rounding_guard(False)
-    backend.synchronize()
-    del g_out
-    rm = det.rounding_margin(reset=True)
-    ex = det.exactness()
-    exactness = {"observed_margin": [float(f"{v:.4g}") for v in rm["observed"]],
-                 "apriori_bound": [round(v, 4) for v in rm["apriori"]],
-                 "certified": all(o < 1 - e for o, e in zip(rm["observed"], rm["apriori"])),
-                 "guarded_output_identical": identical,
-                 "guarded_every_launch": ex["guarded"], "breaches": ex["breaches"],
-                 # what a key with E >= 0.5 (guarded on every launch, exactness contract) would cost:
-                 # the same detect through the guarded kernels + their no-op fallbacks + the folds
-                 "guarded_ms_per_step": round(guarded_ms, 1),
-                 "guarded_over_timed": round(guarded_ms / (elapsed / args.steps * 1e3), 4),
-                 "note": "level 1, level 2: largest |y - rint(y)| over every rounded FFT product coefficient "
-                         "of one untimed guarded pass; exact when observed < 1 - apriori (DESIGN.md §3a); a "
-                         "level with apriori >= 0.5 would be guarded on every launch (omr_ctx_exactness)"}
+    time_info = exactness = ok = e2e = latency_ms = latency_tp_ms = None
+    if args.full:
+        # Detector::detect_with_time_info's split (detector.rs:169-221) on one untimed pass: timing
+        # mode 2 runs the level-2 rotation and the trace as two launches, so the trace gets its own time
+        det.enable_timing(2)
+        backend.detect(d_ca, d_cb, out=d_out)
+        split = det.last_timing()
+        det.enable_timing(0)
+        backend.synchronize()
+        time_info = {"total_detect_ms": round(split["total_ms"], 2),
+                     "first_level_bootstrapping_ms": round(split["first_level_ms"], 2),
+                     "second_level_bootstrapping_ms": round(split["second_level_ms"], 2),
+                     "trace_ms": round(split["trace_ms"], 2),
+                     "key_switch_ms": round(split["key_switch_ms"], 2), "messages": int(split["messages"]),
+                     "trace_separate": bool(split["trace_separate"]),
+                     "note": "one untimed detect pass in timing mode 2 (trace as its own launch); DetectTimeInfo "
+                             "fields (detector.rs:51-57), first level includes the key switch"}
 
-    # correctness spot check on this rank's data: the client decrypts (library Retriever, CPU)
-    # and every pertinency ciphertext must decode to [1, 0, ..., 0] or all zeros (omd.rs:48-58)
-    host = d_out[: min(D, 256)].cpu().numpy().view(np.uint64)
-    dec = A.Retriever(A.RetrievalParams(max(1, total), 1), pack_a).decrypt_decode(host)
-    ok = bool(np.array_equal(dec[:, 0] == 1, mask[: host.shape[0]]) and not dec[:, 1:].any())
+        # Exactness certificate of the FFT external products on this run's clues: one
+        # untimed pass through the guarded kernels records the largest |y - rint(y)| of every rounded
+        # coefficient; with the key's a priori bound E the run is exact when margin < 1 - E. The pass runs
+        # in slices of at most one launch (--batch), each compared with the timed output: the extra
+        # device memory is one slice whatever D is.
+        det.rounding_margin(reset=True)
+        det.set_rounding_guard(True)
+        G = min(D, args.batch)
+        g_out = torch.empty((G, 2, 2048), dtype=torch.int64, device=dev)
+        identical = True
+        guarded_ms = 0.0
+        for s0 in range(0, D, G):
+            n = min(G, D - s0)
+            torch.cuda.synchronize(dev)
+            tg = time.perf_counter()
+            det.detect_batch_device(d_ca[s0:].data_ptr(), d_cb[s0:].data_ptr(), n, g_out.data_ptr(), stream.cuda_stream)
+            torch.cuda.synchronize(dev)
+            guarded_ms += (time.perf_counter() - tg) * 1e3
+            identical &= bool(torch.equal(g_out[:n], d_out[s0:s0 + n]))
+        det.set_rounding_guard(False)
+        backend.synchronize()
+        del g_out
+        rm = det.rounding_margin(reset=True)
+        ex = det.exactness()
+        exactness = {"observed_margin": [float(f"{v:.4g}") for v in rm["observed"]],
+                     "apriori_bound": [round(v, 4) for v in rm["apriori"]],
+                     "certified": all(o < 1 - e for o, e in zip(rm["observed"], rm["apriori"])),
+                     "guarded_output_identical": identical,
+                     "guarded_every_launch": ex["guarded"], "breaches": ex["breaches"],
+                     # what a key with E >= 0.5 (guarded on every launch, exactness contract) would cost:
+                     # the same detect through the guarded kernels + their no-op fallbacks + the folds
+                     "guarded_ms_per_step": round(guarded_ms, 1),
+                     "guarded_over_timed": round(guarded_ms / (elapsed / args.steps * 1e3), 4),
+                     "note": "level 1, level 2: largest |y - rint(y)| over every rounded FFT product coefficient "
+                             "of one untimed guarded pass; exact when observed < 1 - apriori (DESIGN.md §3a); a "
+                             "level with apriori >= 0.5 would be guarded on every launch (omr_ctx_exactness)"}
 
-    e2e = None
-    if not args.no_e2e:
-        rp = A.RetrievalParams(total, len(pert))
-        weights = A.payload_weights(WEIGHT_SEED, rp)
-        digest, et = omr_dist.encode_and_reduce(backend, d_out, synthetic_payloads(first, D), first, total, rp,
-                                                INDEX_SEED, weights, dist)
-        if rank == 0:
-            t3 = time.perf_counter()
-            indices, pays = A.Retriever(rp, pack_a).decode_digest(digest.indices, digest.payloads, WEIGHT_SEED)
-            t4 = time.perf_counter()
-            good = indices == [int(v) for v in pert]
-            if good:
-                want = np.concatenate([synthetic_payloads(int(i), 1) for i in indices]) if indices else np.zeros((0, 612))
-                good = bool(np.array_equal(pays, want))
-            e2e = {"ok": good, "encode_ms": round(et["encode_s"] * 1e3, 2),
-                   "encode_reduce_ms": round(et["encode_reduce_s"] * 1e3, 2), "retrieve_ms": round((t4 - t3) * 1e3, 2),
-                   "index_ct": rp.max_encode_indices_cipher_count, "payload_ct": rp.cmb_cipher_count,
-                   "digest_bytes": int((rp.max_encode_indices_cipher_count + rp.cmb_cipher_count) * 2 * 2048 * 8),
-                   "collective": "reduce(sum) over RCCL" if dist else "none", "pertinent_recovered": len(indices)}
+        # correctness spot check on this rank's data: the client decrypts (library Retriever, CPU)
+        # and every pertinency ciphertext must decode to [1, 0, ..., 0] or all zeros (omd.rs:48-58)
+        host = d_out[: min(D, 256)].cpu().numpy().view(np.uint64)
+        dec = A.Retriever(A.RetrievalParams(max(1, total), 1), pack_a).decrypt_decode(host)
+        ok = bool(np.array_equal(dec[:, 0] == 1, mask[: host.shape[0]]) and not dec[:, 1:].any())
 
-    latency_ms = latency_tp_ms = None
-    if not args.no_latency:
-        # one message end to end (detect on device buffers, wall clock): the latency kernels
-        # (default for chunks up to 64 messages) and, for comparison, the throughput kernels
-        one_out = torch.empty((1, 2, 2048), dtype=torch.int64, device=dev)
+        if not args.no_e2e:
+            rp = A.RetrievalParams(total, len(pert))
+            weights = A.payload_weights(WEIGHT_SEED, rp)
+            digest, et = omr_dist.encode_and_reduce(backend, d_out, synthetic_payloads(first, D), first, total, rp,
+                                                    INDEX_SEED, weights, dist)
+            if rank == 0:
+                t3 = time.perf_counter()
+                indices, pays = A.Retriever(rp, pack_a).decode_digest(digest.indices, digest.payloads, WEIGHT_SEED)
+                t4 = time.perf_counter()
+                good = indices == [int(v) for v in pert]
+                if good:
+                    want = (np.concatenate([synthetic_payloads(int(i), 1) for i in indices]) if indices
+                            else np.zeros((0, 612)))
+                    good = bool(np.array_equal(pays, want))
+                e2e = {"ok": good, "encode_ms": round(et["encode_s"] * 1e3, 2),
+                       "encode_reduce_ms": round(et["encode_reduce_s"] * 1e3, 2), "retrieve_ms": round((t4 - t3) * 1e3, 2),
+                       "index_ct": rp.max_encode_indices_cipher_count, "payload_ct": rp.cmb_cipher_count,
+                       "digest_bytes": int((rp.max_encode_indices_cipher_count + rp.cmb_cipher_count) * 2 * 2048 * 8),
+                       "collective": "reduce(sum) over RCCL" if dist else "none", "pertinent_recovered": len(indices)}
 
-        def one_message():
-            lat = []
-            for _ in range(3):
-                torch.cuda.synchronize(dev)
-                t1 = time.perf_counter()
-                det.detect_batch_device(d_ca.data_ptr(), d_cb.data_ptr(), 1, one_out.data_ptr(), stream.cuda_stream)
-                torch.cuda.synchronize(dev)
-                lat.append((time.perf_counter() - t1) * 1e3)
-                det.check(stream.cuda_stream)  # raises on a failed two-CU hand-off
-                if not torch.equal(one_out[0], d_out[0]):  # same message as the timed throughput pass
-                    raise RuntimeError("single-message detect differs from the throughput kernels' output")
-            return round(min(lat), 3)
+        if not args.no_latency:
+            # one message end to end (detect on device buffers, wall clock): the latency kernels
+            # (default for chunks up to 64 messages) and, for comparison, the throughput kernels
+            one_out = torch.empty((1, 2, 2048), dtype=torch.int64, device=dev)
 
-        latency_ms = one_message()
-        det.set_latency_threshold(0)
-        latency_tp_ms = one_message()
-        det.set_latency_threshold(64)
+            def one_message():
+                lat = []
+                for _ in range(3):
+                    torch.cuda.synchronize(dev)
+                    t1 = time.perf_counter()
+                    det.detect_batch_device(d_ca.data_ptr(), d_cb.data_ptr(), 1, one_out.data_ptr(), stream.cuda_stream)
+                    torch.cuda.synchronize(dev)
+                    lat.append((time.perf_counter() - t1) * 1e3)
+                    det.check(stream.cuda_stream)  # raises on a failed two-CU hand-off
+                    if not torch.equal(one_out[0], d_out[0]):  # same message as the timed throughput pass
+                        raise RuntimeError("single-message detect differs from the throughput kernels' output")
+                return round(min(lat), 3)
+
+            latency_ms = one_message()
+            det.set_latency_threshold(0)
+            latency_tp_ms = one_message()
+            det.set_latency_threshold(64)
 
     if rank != 0:
         if dist:
@@ -526,35 +572,38 @@ def main():
 
     msgs = args.steps * total
     value = msgs / elapsed
-    names = A.detect_kernels()
-    # per-kernel launch times: level 2's rotation (br2f_kernel) and its trace (trace_fft_kernel) are
-    # separate launches since round 5, so the rotation's time is second_level alone
-    kms = {"br1": stage["first_level_ms"] - stage["key_switch_ms"], "ks": stage["key_switch_ms"],
-           "br2": stage["second_level_ms"]}
-    role = max(kms, key=kms.get)
-    chunks = -(-D // args.batch)
-    roof, hbm = rooflines(role, names[role], args.steps * chunks, D / chunks, kms[role], value, world, names)
-    # the other blind rotation's roofline the same way (its own live launch time and counted FLOPs)
+    roof = hbm = detect_fp64 = None
     other_roofs = {}
-    for r in ("br1", "br2"):
-        if r != role:
-            ro, _ = rooflines(r, names[r], args.steps * chunks, D / chunks, kms[r], value, world, names)
-            if ro is not None:
-                other_roofs[r] = ro
-    # whole-detect FP64 fractions: counted FLOPs (profiles/compute_latest.json, FMA = 2) and the fixed
-    # algorithmic FLOPs (FIXED_FLOP_PER_MSG), both at the whole job's per-GPU rate
-    comp = load_profile("compute_latest.json") or {}
-    ck = comp.get("kernels", {})
-    counted = sum(ck.get(n, {}).get("fp64_flop_per_msg", 0.0) for n in (names["br1"], names["br2"], "trace_fft_kernel"))
-    rate = value / world
-    detect_fp64 = {"counted_flop_per_msg": round(counted), "fixed_flop_per_msg": sum(FIXED_FLOP_PER_MSG.values()),
-                   "detect_fp64_frac": round(counted * rate / 1e12 / FP64_PEAK_TFLOPS, 4) if counted else None,
-                   "detect_fp64_frac_fixed_work": round(sum(FIXED_FLOP_PER_MSG.values()) * rate / 1e12
-                                                        / FP64_PEAK_TFLOPS, 4),
-                   "peak_tflops": round(FP64_PEAK_TFLOPS, 2), "counts_from": comp.get("source"),
-                   "note": "FP64 FLOPs of the whole detect (both rotations + the FFT trace) per message x the "
-                           "per-GPU msg/s over the FP64 peak; fixed_work: the constant algorithmic count of "
-                           "DESIGN.md §5 (10 FLOPs per radix-2 butterfly, 8 per complex MAC)"}
+    if args.full:
+        names = A.detect_kernels()
+        # per-kernel launch times: level 2's rotation (br2f_kernel) and its trace (trace_fft_kernel) are
+        # separate launches since round 5, so the rotation's time is second_level alone
+        kms = {"br1": stage["first_level_ms"] - stage["key_switch_ms"], "ks": stage["key_switch_ms"],
+               "br2": stage["second_level_ms"]}
+        role = max(kms, key=kms.get)
+        chunks = -(-D // args.batch)
+        roof, hbm = rooflines(role, names[role], args.steps * chunks, D / chunks, kms[role], value, world, names)
+        # the other blind rotation's roofline the same way (its own live launch time and counted FLOPs)
+        other_roofs = {}
+        for r in ("br1", "br2"):
+            if r != role:
+                ro, _ = rooflines(r, names[r], args.steps * chunks, D / chunks, kms[r], value, world, names)
+                if ro is not None:
+                    other_roofs[r] = ro
+        # whole-detect FP64 fractions: counted FLOPs (profiles/compute_latest.json, FMA = 2) and the fixed
+        # algorithmic FLOPs (FIXED_FLOP_PER_MSG), both at the whole job's per-GPU rate
+        comp = load_profile("compute_latest.json") or {}
+        ck = comp.get("kernels", {})
+        counted = sum(ck.get(n, {}).get("fp64_flop_per_msg", 0.0) for n in (names["br1"], names["br2"], "trace_fft_kernel"))
+        rate = value / world
+        detect_fp64 = {"counted_flop_per_msg": round(counted), "fixed_flop_per_msg": sum(FIXED_FLOP_PER_MSG.values()),
+                       "detect_fp64_frac": round(counted * rate / 1e12 / FP64_PEAK_TFLOPS, 4) if counted else None,
+                       "detect_fp64_frac_fixed_work": round(sum(FIXED_FLOP_PER_MSG.values()) * rate / 1e12
+                                                            / FP64_PEAK_TFLOPS, 4),
+                       "peak_tflops": round(FP64_PEAK_TFLOPS, 2), "counts_from": comp.get("source"),
+                       "note": "FP64 FLOPs of the whole detect (both rotations + the FFT trace) per message x the "
+                               "per-GPU msg/s over the FP64 peak; fixed_work: the constant algorithmic count of "
+                               "DESIGN.md §5 (10 FLOPs per radix-2 butterfly, 8 per complex MAC)"}
 
     def spread(v):
         v = sorted(v)
@@ -605,7 +654,9 @@ def main():
         "e2e": e2e,
         "setup_s": round(setup_s, 1),
     }
-    if not args.no_cpu_baseline and world == 1:
+    if not args.full:
+        line = {k: v for k, v in line.items() if k not in FULL_ONLY_KEYS}
+    if args.full and not args.no_cpu_baseline and world == 1:
         n = max(args.cpu_single_msgs, args.cpu_msgs_per_thread * cpu_threads())
         dk = A.DetectionKey(*[b.cpu().numpy().view(np.uint32 if b.dtype == torch.int32 else np.uint64).reshape(shape)
                               for b, shape in zip(kbufs, (A.BSK1_SHAPE, A.KSK_SHAPE, A.BSK2_SHAPE, A.TK_SHAPE))])

@@ -293,7 +293,7 @@ def test_bench_two_ranks_one_device_rehearsal():
     all-reduce timing, the digest reduce, rank 0's single JSON line, rank 1's early return."""
     import json
     r = _run_bench(["--gpus", "2", "--one-device", "--messages", "2048", "--steps", "1", "--warmup", "0",
-                    "--batch", "2048"])
+                    "--batch", "2048", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -322,3 +322,37 @@ def test_bench_two_ranks_one_device_child_failure():
                    env_extra={"OMR_BENCH_FAIL_RANK": "1"}, timeout=300)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     assert r.stdout.strip() == ""
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain bench.py run reports the headline fields only (everything else is behind --full),
+    --steps sets the number of timed steps, and --dump-outputs writes the last timed step's
+    pertinency vector: at D = 1,100 (two launches of --batch 1,024) a fixed sample of 1,024 rows,
+    float64 holding the residues exactly; the client decrypts every dumped row to [1, 0, ..., 0]
+    where bench.py's seeded pertinent set says so and to zeros elsewhere."""
+    import json
+    D = 1100
+    r = _run_bench(["--gpus", "1", "--messages", str(D), "--steps", "2", "--warmup", "1", "--batch", "1024",
+                    "--dump-outputs", str(tmp_path / "dump")], timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["unit"] == "messages/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 2 and r.stderr.count("step 2/2 done") == 1 and "step 3/" not in r.stderr
+    assert line["ms_per_step"] > 0 and abs(line["value"] - D / (line["ms_per_step"] / 1e3)) < 0.02 * line["value"]
+    for k in ("correct", "exactness", "e2e", "roofline", "hbm", "cpu_baseline", "latency_ms_per_message",
+              "detect_time_info", "detect_fp64"):
+        assert k not in line, k
+    assert sorted(os.listdir(tmp_path / "dump")) == ["pertinency.npy", "pertinency_rows.npy"]
+    out, rows = np.load(tmp_path / "dump" / "pertinency.npy"), np.load(tmp_path / "dump" / "pertinency_rows.npy")
+    assert out.dtype == np.float64 and out.shape == (1024, 2, 2048) and rows.dtype == np.float64
+    rows = rows.astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < D
+    assert out.min() >= 0 and out.max() < A.Q2
+    mask = np.zeros(D, dtype=bool)
+    mask[np.random.default_rng(2025).choice(D, 50, replace=False)] = True  # bench.py's pertinent set
+    pack_a = A.SecretKeyPack(PL.SK_SEED)
+    dec = A.Retriever(A.RetrievalParams(D, 1), pack_a).decrypt_decode(out.astype(np.uint64))
+    assert np.array_equal(dec[:, 0] == 1, mask[rows]) and not dec[:, 1:].any()
+    assert mask[rows].sum() >= 40  # the sample holds pertinent rows (1,024 of 1,100)

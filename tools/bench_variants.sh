@@ -3,6 +3,7 @@
 #   tools/bench_variants.sh [D] [extra bench.py flags, e.g. --no-e2e for timing-only ablation builds]
 D=${1:-65536}
 shift
+set -- --full "$@"  # correct / e2e are reported by a --full run only
 mkdir -p gpurun_out
 for so in tfhe-omr_amd/build/var_*.so; do
   OMR_GPU_LIB=$PWD/$so timeout -k 10 300 python bench.py --messages $D --steps 1 --warmup 1 --no-cpu-baseline --no-latency "$@" > gpurun_out/bv.json 2>> gpurun_out/bench_variants.err

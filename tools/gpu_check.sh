@@ -5,4 +5,4 @@ set -o pipefail
 tag=${1:-check}
 mkdir -p gpurun_out/$tag
 tools/gpu_step.sh 600 $tag/gpu_tests.log python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread &&
-tools/gpu_step.sh 400 $tag/bench.log python bench.py
+tools/gpu_step.sh 400 $tag/bench.log python bench.py --full
