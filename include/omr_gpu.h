@@ -141,7 +141,10 @@ omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const uint64_t *
  * Detector — one context per GPU; calls on one context are serialised; contexts are
  * independent. Detector::new (detector.rs:85-110) uploads the keys and converts them to the
  * device layout; the LUTs (:457-503) are built inside. The key view may point to host memory
- * or to device memory of `device` (e.g. from omr_keygen_detection_key_device).
+ * or to device memory of `device` (e.g. from omr_keygen_detection_key_device). The context
+ * keeps a 32 MB host copy of BSK1 until level 1's exact-NTT key is first needed
+ * (omr_ctx_set_rounding_guard / omr_ctx_set_exact_level1, or at creation when level 1 is guarded
+ * by the exactness contract); the copy is dropped once that key is built.
  * ------------------------------------------------------------------------------------- */
 typedef struct omr_ctx omr_ctx;
 
@@ -186,7 +189,11 @@ omr_status omr_ctx_check(omr_ctx *ctx, void *hip_stream);
  * (from kappa[l], the largest stored key-spectrum magnitude, computed at context creation): if
  * E < 0.5 the rounding is exact for every input; a run with observed < 1 - E is exact (an error
  * |e| in [0.5, E] would show a margin >= 1 - E). Any pointer may be NULL; reset != 0 zeroes the
- * observed margins after reading them. The read synchronises the device. */
+ * observed margins after reading them. The read synchronises the device.
+ * The first enable on a context (of this or of omr_ctx_set_exact_level1) builds level 1's exact-NTT
+ * key: it allocates 64 MB of device memory and runs a blocking conversion under the context mutex
+ * (other calls on the context wait), and can fail with OMR_ERR_DEVICE or OMR_ERR_OUT_OF_MEMORY;
+ * the setting is then unchanged. */
 omr_status omr_ctx_set_rounding_guard(omr_ctx *ctx, int enable);
 omr_status omr_ctx_rounding_margin(omr_ctx *ctx, double observed[2], double apriori[2],
                                    double kappa[2], int reset);
@@ -204,7 +211,10 @@ omr_status omr_ctx_exactness(omr_ctx *ctx, int guarded[2], uint64_t breaches[2])
 /* Level 1 on the exact modular NTT for every launch of the context (br1n_kernel: the reference's
  * own arithmetic, concrete-ntt in BlindRotationKey::blind_rotate, detector.rs:553-557), instead of the
  * FFT kernels; enable = 0 restores them. Outputs are bit-identical either way -- a cross-check of
- * the FFT path at any size, about 3x slower at level 1. */
+ * the FFT path at any size, about 3x slower at level 1.
+ * The first enable on a context (of this or of omr_ctx_set_rounding_guard) builds the exact-NTT
+ * key: it allocates 64 MB of device memory and runs a blocking conversion under the context mutex,
+ * and can fail with OMR_ERR_DEVICE or OMR_ERR_OUT_OF_MEMORY; the setting is then unchanged. */
 omr_status omr_ctx_set_exact_level1(omr_ctx *ctx, int enable);
 /* Diagnostics: `count` stored key-spectrum values (complex, re/im pairs) starting at value `first`
  * of level 1 (BSK1, [512][8][2][512], /512) or level 2 (BSK2 limbs, [670][12][2][2][1024], /1024),

@@ -1,5 +1,5 @@
 """A priori bound on the rounding error of the FFT external products, restated
-from the coefficient-domain key with numpy -- the same formula context.hip's apriori_bound
+from the coefficient-domain key with numpy -- the same formula host_tables.hpp's apriori_bound
 evaluates on the device-stored double-double key spectra at context creation:
 
   E = n D (1 + 2^-30) max over steps i and output spectra o of
@@ -49,7 +49,7 @@ def apriori_bounds(dk, q1=134215681, q2=1125899906826241):
 
 
 def apriori_bound_latency2(dk, q2=1125899906826241):
-    """Level 2 as br2y_kernel (the latency path) accumulates it (context.hip, apriori_bound level 3):
+    """Level 2 as br2y_kernel (the latency path) accumulates it (host_tables.hpp, apriori_bound level 3):
     each group chains its three rows (weights 6, 4, 2), then two additions: 8 - 2 j for digit
     3 g + j of either polynomial."""
     r2 = _centred(dk.bsk2.reshape(670, 12, 2, 2048), q2)
@@ -59,7 +59,7 @@ def apriori_bound_latency2(dk, q2=1125899906826241):
 
 
 def apriori_bound_trace(dk, q2=1125899906826241):
-    """The FFT trace (br2f_trace; context.hip, apriori_bound level 4): 11 steps, 25 rows of the trace
+    """The FFT trace (br2f_trace; host_tables.hpp, apriori_bound level 4): 11 steps, 25 rows of the trace
     key [11][25][2 out][2048] as two 25-bit limbs, digits |d| <= 3 (balanced base 4, the top one in
     [-2, 3]), accumulated in row order."""
     r = _centred(dk.trace_key.reshape(11, 25, 2, 2048), q2)

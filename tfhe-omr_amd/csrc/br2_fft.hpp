@@ -339,13 +339,8 @@ __device__ __forceinline__ void br2f_load_half(double2 (&k)[2][Fft1024::E], __am
   for (int l = 0; l < 2; ++l)
 #pragma unroll
     for (int e = 0; e < Fft1024::E; ++e) {
-#ifdef OMR_BR2_KEYABL  // timing-only ablation: every key load from one 4 KB block (L1-resident; wrong output)
-      const uint32_t soff = 0;
-      (void)q;
-#else
       const uint32_t soff = (uint32_t)q * (uint32_t)(BR2_ROW * sizeof(double2)) +
                             (uint32_t)(((o * 2 + l) * Fft1024::n + e * Fft1024::T) * sizeof(double2));
-#endif
       k[l][e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, t16, (int)soff, 0));
     }
 }
@@ -398,12 +393,8 @@ __device__ __forceinline__ void br2f_digit(const uint32_t (&pk)[2][Fft1024::E][D
   auto load_kb = [&](int l) {
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-#ifdef OMR_BR2_KEYABL
-      const uint32_t soff = 0;
-#else
       const uint32_t soff = (uint32_t)q * (uint32_t)(BR2_ROW * sizeof(double2)) +
                             (uint32_t)(((1 * 2 + l) * Fft1024::n + e * Fft1024::T) * sizeof(double2));
-#endif
       kb[l][e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, t16, (int)soff, 0));
     }
   };
@@ -938,20 +929,10 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
     if (a == 0) continue;  // (X^0 - 1) * ACC = 0 (both workgroups of the message skip it)
     OMR_PHASE(pslot, (int)hc, 0);
     const int q0 = i * 2 * D2 + r * D2 + 3 * g;  // the group's first GGSW row of this step
-#ifdef OMR_BR2Y_NOKEY
-#define br2y_load(...) ((void)0)
-    if (i == 0 || pre == -1) {
-      br2f_load_half(ka, rsrc, q0, 0, t16);
-      br2f_load_half(kb, rsrc, q0, 1, t16);
-      pre = -2;
-    }
-#else
-#define br2y_load(...) br2f_load_half(__VA_ARGS__)
     if (pre != i) {
       br2f_load_half(ka, rsrc, q0, 0, t16);
       br2f_load_half(kb, rsrc, q0, 1, t16);
     }
-#endif
     wg_barrier_lds();  // ACC_r (init or the previous update) visible; the previous step's LDS reads done
     uint32_t pw[2][E];  // word g of the digits at the thread's P0 points (coefficients j, j + 1024)
     {
@@ -992,9 +973,9 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
           }
         if (j < 2) {
           if (o == 0)
-            br2y_load(ka, rsrc, q0 + j + 1, 0, t16);
+            br2f_load_half(ka, rsrc, q0 + j + 1, 0, t16);
           else
-            br2y_load(kb, rsrc, q0 + j + 1, 1, t16);
+            br2f_load_half(kb, rsrc, q0 + j + 1, 1, t16);
         }
       }
     }
@@ -1040,7 +1021,6 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
         const double2 vr = qr[e * T + t], vh = qh[e * T + t];
         fr[e] = pr4[0][e] + vr.x;
         fi[e] = pi4[0][e] + vr.y;
-#ifndef OMR_BR2Y_NOHANDOFF  // timing-only ablation: no payload crosses (wrong output)
         if (fast) {  // plain stores: the lines stay in this XCD's L2 for the partner's sc1 loads
           dst[e * T + t] = pr4[2][e] + vh.x;
           dst[n + e * T + t] = pi4[2][e] + vh.y;
@@ -1048,15 +1028,8 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
           st_sc1(dst + e * T + t, pr4[2][e] + vh.x);  // limb g of output 1 - r: the partner's
           st_sc1(dst + n + e * T + t, pi4[2][e] + vh.y);
         }
-#else
-        (void)dst;
-        (void)vh;
-        (void)their_flag;
-#endif
       }
-#ifndef OMR_BR2Y_NOHANDOFF
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     }
     __syncthreads();
     OMR_PHASE(pslot, (int)hc, 4);
@@ -1065,7 +1038,6 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
         __hip_atomic_store(my_flag, hc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // plain store
       else
         __hip_atomic_store(my_flag, hc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifndef OMR_BR2Y_NOHANDOFF
       int k = 0;
       while (__hip_atomic_load(their_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < hc + 1) {
         if (++k == BR2X_SPIN) {
@@ -1075,7 +1047,6 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
         }
         __builtin_amdgcn_s_sleep(2);
       }
-#endif
     }
     __syncthreads();
     OMR_PHASE(pslot, (int)hc, 5);
@@ -1084,23 +1055,17 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
       const double *src = xg + ((((size_t)m * 2 + (1 - r)) * 2 + (hc & 1)) * 2 + g) * 2 * n;
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-#ifndef OMR_BR2Y_NOHANDOFF
         fr[e] += ld_sc1(src + e * T + t);
         fi[e] += ld_sc1(src + n + e * T + t);
-#else
-        (void)src;
-#endif
       }
     }
     asm volatile("" : "+v"(fr[0]), "+v"(fr[1]), "+v"(fr[2]), "+v"(fr[3]), "+v"(fi[0]), "+v"(fi[1]), "+v"(fi[2]),
                  "+v"(fi[3])::"memory");  // consumed before the prefetch below is issued
-#ifndef OMR_BR2Y_NOKEY
     if (i + 1 < NI) {  // the next step's first row (kept when that step runs next)
       br2f_load_half(ka, rsrc, q0 + 2 * D2, 0, t16);
       br2f_load_half(kb, rsrc, q0 + 2 * D2, 1, t16);
       pre = i + 1;
     }
-#endif
     F::inv(fr, fi, xb[g][1], tws, t);  // X1: every reader of the limb swap passed the hand-off barriers
     OMR_PHASE(pslot, (int)hc, 6);
     // round limb g; the groups swap halves: group g recombines the coefficients idx(0, t, e) + 1024 g

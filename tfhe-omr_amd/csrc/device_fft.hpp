@@ -116,7 +116,7 @@ struct WgFft {
   static constexpr int T = T_, E = E_, L = L_, N = T * E;
   static_assert(T == 64 && E == 8 && L == 9, "written for the level-1 geometry: one wave, 64 x 8");
   static constexpr int BUF = N;  // LDS slots (double2) per transform
-  // twiddle table offsets (double2 entries; fft_twiddles() in context.hip writes them)
+  // twiddle table offsets (double2 entries; fft_twiddles() in host_tables.hpp writes them)
   static constexpr int TW_P0I = 0, TW_P0F = 7, TW_P1 = 11, TW_P2I = 27, TW_P2F = 251, TW_P3 = 379, TW_LEN = 507;
   static_assert(TW_LEN <= N, "the table is copied to an N-entry LDS array");
 

@@ -11,7 +11,7 @@
 //  - kappa_r, the largest |K^| of every stored key row (row_max_abs_kernel): the only key-dependent
 //    constants of the a priori bound on |computed - exact| of every rounded product coefficient,
 //    E = n D max over steps and outputs of [(2 delta_f + u') sum_r kappa_r + sqrt(2) u sum_k w_k
-//    kappa_r(k)] (context.hip: apriori_bound);
+//    kappa_r(k)] (host_tables.hpp: apriori_bound);
 //  - the rounding-margin guard (RoundGuard): the guarded kernel variants record the largest
 //    |y - rint(y)| over every rounded product coefficient and publish it with one 64-bit atomic
 //    max per wave. If E < 0.5 the rounding is exact for every input; otherwise a run whose

@@ -106,7 +106,8 @@ inline uint64_t to_mod(int64_t v, uint64_t q) {
   int64_t r = v % (int64_t)q;
   return (uint64_t)(r < 0 ? r + (int64_t)q : r);
 }
-
+// canonical residue -> its centred representative as a double (the device tables' convention)
+inline double centred(uint64_t v, uint64_t q) { return v > (q - 1) / 2 ? (double)v - (double)q : (double)v; }
 
 }  // namespace omr
 

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_util.hpp"
 #include "host_ring.hpp"
 #include "kernels.hpp"
 #include "rng.hpp"
@@ -24,13 +25,6 @@
 using namespace omr;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return set_error(OMR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int CDT_LDS = 64;  // CDT tables up to this size are searched from LDS
 constexpr int SLACK = 32;    // rejected uniform draws a row may absorb before it reports overrun
@@ -316,28 +310,9 @@ __global__ __launch_bounds__(64) void ksk_rows_kernel(uint64_t seed, const uint8
   }
 }
 
-template <typename T>
-struct DevMem {
-  T *p = nullptr;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t put(const T *src, size_t n, hipStream_t st) {
-    hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e != hipSuccess || n == 0) return e;
-    return hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, st);
-  }
-  template <class V>
-  hipError_t put(const V &v, hipStream_t st) {
-    return put(v.data(), v.size(), st);
-  }
-};
-
-double centred_d(uint64_t v, uint64_t q) { return v > (q - 1) / 2 ? (double)v - (double)q : (double)v; }
-
 std::vector<double> centred_vec(const std::vector<uint64_t> &v, uint64_t q) {
   std::vector<double> r(v.size());
-  for (size_t i = 0; i < v.size(); ++i) r[i] = centred_d(v[i], q);
+  for (size_t i = 0; i < v.size(); ++i) r[i] = centred(v[i], q);
   return r;
 }
 
@@ -355,14 +330,14 @@ extern "C" omr_status omr_gen_clues_device(const omr_secret_key_pack *sk, uint64
     return set_error(OMR_ERR_DEVICE, "omr_gen_clues_device: CDT table too large");
   std::vector<uint16_t> pk(sk->pk_a, sk->pk_a + N0);
   pk.insert(pk.end(), sk->pk_b, sk->pk_b + N0);
-  DevMem<uint16_t> dpk;
-  DevMem<uint64_t> dcdt;
-  HIP_TRY(dpk.put(pk, st));
-  HIP_TRY(dcdt.put(g.table(), st));
+  DevBuf<uint16_t> dpk;
+  DevBuf<uint64_t> dcdt;
+  HIP_TRY(dpk.upload(pk, st));
+  HIP_TRY(dcdt.upload(g.table(), st));
   constexpr size_t CHUNK = 1u << 20;
   for (size_t off = 0; off < count; off += CHUNK) {
     const size_t n = std::min(CHUNK, count - off);
-    gen_clues_kernel<<<(unsigned)n, 64, 0, st>>>(dpk.p, dcdt.p, (int)g.table().size(), seed, first + off, n,
+    gen_clues_kernel<<<(unsigned)n, 64, 0, st>>>(dpk, dcdt, (int)g.table().size(), seed, first + off, n,
                                                 d_clue_a + off * N0, d_clue_b + off * CLUES);
     HIP_TRY(hipGetLastError());
   }
@@ -403,46 +378,46 @@ extern "C" omr_status omr_keygen_detection_key_device(const omr_secret_key_pack 
     }
     for (int j = 0; j < DT; ++j) tscale[(size_t)k * DT + j] = (1ull << (2 * j)) % Q2;
   }
-  DevMem<double> dtw1, ditw1, dtw2, ditw2, ds1, ds2;
-  DevMem<uint64_t> dmg1, dmg2, dscale, dc1, dcks, dc2, dct;
-  DevMem<int8_t> dsgs, dsk1;
-  DevMem<uint8_t> dsint;
-  DevMem<int> dover;
+  DevBuf<double> dtw1, ditw1, dtw2, ditw2, ds1, ds2;
+  DevBuf<uint64_t> dmg1, dmg2, dscale, dc1, dcks, dc2, dct;
+  DevBuf<int8_t> dsgs, dsk1;
+  DevBuf<uint8_t> dsint;
+  DevBuf<int> dover;
   const int zero = 0;
-  HIP_TRY(dtw1.put(centred_vec(T1.w, Q1), st));
-  HIP_TRY(ditw1.put(centred_vec(T1.iw, Q1), st));
-  HIP_TRY(dtw2.put(centred_vec(T2.w, Q2), st));
-  HIP_TRY(ditw2.put(centred_vec(T2.iw, Q2), st));
-  HIP_TRY(ds1.put(centred_vec(sk->s1_ntt, Q1), st));
-  HIP_TRY(ds2.put(centred_vec(sk->s2_ntt, Q2), st));
-  HIP_TRY(dmg1.put(mg1, st));
-  HIP_TRY(dmg2.put(mg2, st));
-  HIP_TRY(dscale.put(tscale, st));
-  HIP_TRY(dsgs.put(sgs, st));
-  HIP_TRY(dsk1.put(sk->s1, N1, st));
-  HIP_TRY(dsint.put(sk->sint, NI, st));
-  HIP_TRY(dc1.put(g1.table(), st));
-  HIP_TRY(dcks.put(gks.table(), st));
-  HIP_TRY(dc2.put(g2.table(), st));
-  HIP_TRY(dct.put(gt.table(), st));
-  HIP_TRY(dover.put(&zero, 1, st));
-  RowJob j1{seed, DOM_BSK1, N0 * 2 * D1, D1, dmg1.p, ds1.p, dtw1.p, ditw1.p,
-            centred_d(T1.ninv, Q1), dc1.p, (int)g1.table().size(), nullptr, nullptr, dover.p};
+  HIP_TRY(dtw1.upload(centred_vec(T1.w, Q1), st));
+  HIP_TRY(ditw1.upload(centred_vec(T1.iw, Q1), st));
+  HIP_TRY(dtw2.upload(centred_vec(T2.w, Q2), st));
+  HIP_TRY(ditw2.upload(centred_vec(T2.iw, Q2), st));
+  HIP_TRY(ds1.upload(centred_vec(sk->s1_ntt, Q1), st));
+  HIP_TRY(ds2.upload(centred_vec(sk->s2_ntt, Q2), st));
+  HIP_TRY(dmg1.upload(mg1, st));
+  HIP_TRY(dmg2.upload(mg2, st));
+  HIP_TRY(dscale.upload(tscale, st));
+  HIP_TRY(dsgs.upload(sgs, st));
+  HIP_TRY(dsk1.upload(sk->s1, N1, st));
+  HIP_TRY(dsint.upload(sk->sint, NI, st));
+  HIP_TRY(dc1.upload(g1.table(), st));
+  HIP_TRY(dcks.upload(gks.table(), st));
+  HIP_TRY(dc2.upload(g2.table(), st));
+  HIP_TRY(dct.upload(gt.table(), st));
+  HIP_TRY(dover.upload(&zero, 1, st));
+  RowJob j1{seed, DOM_BSK1, N0 * 2 * D1, D1, dmg1, ds1, dtw1, ditw1,
+            centred(T1.ninv, Q1), dc1, (int)g1.table().size(), nullptr, nullptr, dover};
   rlwe_rows_kernel<1, uint32_t><<<j1.rows, 256, 0, st>>>(j1, d_bsk1);
   HIP_TRY(hipGetLastError());
-  ksk_rows_kernel<<<N1 * KS_DIGITS, 64, 0, st>>>(seed, dsint.p, dsk1.p, dcks.p, (int)gks.table().size(),
-                                                 N1 * KS_DIGITS, d_ksk, dover.p);
+  ksk_rows_kernel<<<N1 * KS_DIGITS, 64, 0, st>>>(seed, dsint, dsk1, dcks, (int)gks.table().size(),
+                                                 N1 * KS_DIGITS, d_ksk, dover);
   HIP_TRY(hipGetLastError());
-  RowJob j2{seed, DOM_BSK2, NI * 2 * D2, D2, dmg2.p, ds2.p, dtw2.p, ditw2.p,
-            centred_d(T2.ninv, Q2), dc2.p, (int)g2.table().size(), nullptr, nullptr, dover.p};
+  RowJob j2{seed, DOM_BSK2, NI * 2 * D2, D2, dmg2, ds2, dtw2, ditw2,
+            centred(T2.ninv, Q2), dc2, (int)g2.table().size(), nullptr, nullptr, dover};
   rlwe_rows_kernel<2, uint64_t><<<j2.rows, 256, 0, st>>>(j2, d_bsk2);
   HIP_TRY(hipGetLastError());
-  RowJob jt{seed, DOM_TK, TRACE_STEPS * DT, 1, nullptr, ds2.p, dtw2.p, ditw2.p,
-            centred_d(T2.ninv, Q2), dct.p, (int)gt.table().size(), dsgs.p, dscale.p, dover.p};
+  RowJob jt{seed, DOM_TK, TRACE_STEPS * DT, 1, nullptr, ds2, dtw2, ditw2,
+            centred(T2.ninv, Q2), dct, (int)gt.table().size(), dsgs, dscale, dover};
   rlwe_rows_kernel<2, uint64_t><<<jt.rows, 256, 0, st>>>(jt, d_tk);
   HIP_TRY(hipGetLastError());
   int over = 0;
-  HIP_TRY(hipMemcpyAsync(&over, dover.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&over, dover, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (over)
     return set_error(OMR_ERR_DEVICE, "omr_keygen_detection_key_device: uniform stream overrun");

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Timing-only ablation of the level-2 key stream (round 6): bench.py at D = 65,536 through the base
-# library and var_keyabl (tools/build_variant.sh keyabl -DOMR_BR2_KEYABL: every key load from one 4 KB
-# block, wrong output), alternating, twice.
+# library and var_keyabl (tools/build_variant.sh keyabl --patch tools/variants/keyabl.patch: every key
+# load from one 4 KB block, wrong output, so the patch never touches the product sources), alternating,
+# twice.
 set -o pipefail
 out=gpurun_out/r06o; mkdir -p $out
 for k in 1 2; do for v in base keyabl; do

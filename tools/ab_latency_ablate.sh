@@ -1,7 +1,8 @@
 #!/bin/bash
 # Timing-only ablations of the latency path's level 2 (round 6): tools/latency_split.py (1 and 7
-# messages) through the base library and the br2y ablation builds (wrong output: no parity run),
-# alternating, twice.
+# messages) through the base library and the br2y ablation builds (wrong output: no parity run; built
+# from patches, tools/build_variant.sh br2y_nokey --patch tools/variants/br2y_nokey.patch and
+# br2y_nohandoff --patch tools/variants/br2y_nohandoff.patch), alternating, twice.
 #   tools/ab_latency_ablate.sh <tag> <variant>...     (tfhe-omr_amd/build/var_<variant>.so)
 set -o pipefail
 tag=$1; shift

@@ -1,5 +1,6 @@
 """Per-phase durations of the latency kernels from a -DOMR_PHASE_TRACE build
-(tools/build_variant.sh phase -DOMR_PHASE_TRACE; OMR_GPU_LIB=.../var_phase.so python tools/phase_trace.py).
+(tools/build_variant.sh phase -DOMR_PHASE_TRACE, a scratch-tree build with the project's Makefile whose
+outputs stay correct; OMR_GPU_LIB=.../var_phase.so python tools/phase_trace.py).
 Runs one single-message detect (latency path) and prints the mean cycles between consecutive phase
 marks of executed steps 200..263 for every traced wave (br1l workgroup 0; br2x workgroups 0, 1)."""
 import ctypes
