@@ -1,5 +1,5 @@
 """The closed-form gadget digits used by the kernels (br1_fft.hpp Lvl1Int::digits/digit,
-detect_kernels.hpp Digits2) equal the recursive signed decomposition of the oracle
+level2_common.hpp Digits2) equal the recursive signed decomposition of the oracle
 (NonPowOf2ApproxSignedBasis: y = floor((v + 2^(drop-1)) / 2^drop), balanced digits, unbounded
 top digit) on boundary and random canonical residues."""
 import numpy as np
@@ -52,7 +52,7 @@ def test_level1_closed_form_digits():
 
 def test_level2_closed_form_digits():
     v = _residues(Q2, 500_000, 2)
-    # detect_kernels.hpp Digits2: bias 64 (1 + 128 + ... + 128^5), exact in FP64 (0 <= y' < 2^43)
+    # level2_common.hpp Digits2: bias 64 (1 + 128 + ... + 128^5), exact in FP64 (0 <= y' < 2^43)
     y = np.floor(v.astype(np.float64) / 256 + 0.5) + 2216338399296.0
     assert y.min() >= 0 and y.max() < 2.0 ** 43
     hi = np.floor(y / 2097152.0)

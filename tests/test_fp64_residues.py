@@ -123,7 +123,7 @@ def test_level2_forward_ntt_bound_with_stage01_tables():
 
 
 def test_level2_mac_four_products_per_reduction():
-    """detect_kernels.hpp cmux_step3: the forward transform output is |x| <= 6.72q, so each
+    """br2_ntt.hpp cmux_mac: the forward transform output is |x| <= 6.72q, so each
     product |mm(x, key)| <= 1.76q (|key| <= q/2), and a reduced sum (|acc| <= q/2 + 2) plus four
     products stays below 7.6q < 8q < 2^53. A fifth product would not fit."""
     b = 6.73

@@ -108,7 +108,7 @@ def real():
 @pytest.fixture(params=["latency", "throughput"])
 def path(request, real):
     """Both kernel families on the same small inputs: the latency kernels (chunks up to 64
-    messages by default, latency_kernels.hpp) and the throughput kernels (threshold 0)."""
+    messages by default, br1_latency.hpp and br2_ntt.hpp) and the throughput kernels (threshold 0)."""
     det = real[1]
     det.set_latency_threshold(64 if request.param == "latency" else 0)
     yield request.param

@@ -8,7 +8,7 @@ Lvl1Int::round_mod), in numpy with explicit u32 wrap-around, against the plain d
 - round_mod(y) in [0, Q] with round_mod(y) = round(y) mod Q, and add(ac'', r) = ac'' + r (mod Q)
   in [0, Q), for FFT outputs y = integer + e (|y| < 2^43, |e| < 0.1), including the multiples of q;
 - and br2f's level-2 digit words (Digits2S: two's-complement fields, one v_bfe_i32 per digit) give
-  the same six digits as Digits2 (detect_kernels.hpp) over the whole canonical range of q2.
+  the same six digits as Digits2 (level2_common.hpp) over the whole canonical range of q2.
 """
 import numpy as np
 
@@ -141,7 +141,7 @@ def test_round_mod_and_update():
 
 # ---- level 2: br2f's signed-field digit words (Digits2S, tfhe-omr_amd/csrc/br2_fft.hpp) --------
 def _digits2_ref(v):
-    """Digits2 (detect_kernels.hpp): biased 7-bit fields (the top one 8 bits wide), minus 64."""
+    """Digits2 (level2_common.hpp): biased 7-bit fields (the top one 8 bits wide), minus 64."""
     y = np.floor(v / 256.0 + 0.5) + 2216338399296.0  # v / 256 is exact: the kernel's fma
     hi = np.floor(y * (1.0 / 2097152.0))
     lo = y - hi * 2097152.0
@@ -236,7 +236,7 @@ def _trace_digits_recursive(v):
 
 
 def _trace_digits_closed(v):
-    """DigitsTrace::pack / get_int (detect_kernels.hpp): the dwords of v + 2 (1 + .. + 4^23) + 1.5 2^52
+    """DigitsTrace::pack / get_int (level2_common.hpp): the dwords of v + 2 (1 + .. + 4^23) + 1.5 2^52
     with every 2-bit field XORed with 2, two's-complement 2-bit fields, the top one 3 bits at 48."""
     b = (v + (187649984473770.0 + 6755399441055744.0)).view(np.uint64)
     w0 = s32(u32((b & np.uint64(0xFFFFFFFF)).astype(np.int64)) ^ 0xAAAAAAAA)

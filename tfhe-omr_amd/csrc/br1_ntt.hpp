@@ -17,9 +17,7 @@
 // Not tuned: a fallback that never runs on a real key, and a test instrument.
 #pragma once
 
-#include "detect_kernels.hpp"
 #include "br1_fft.hpp"
-#include "latency_kernels.hpp"
 
 namespace omr {
 

@@ -24,7 +24,10 @@
 // transforms (2 outputs x 2 limbs) instead of the NTT kernel's 12 + 2 modular transforms.
 #pragma once
 
-#include "latency_kernels.hpp"
+#include "device_fft.hpp"
+#include "exactness.hpp"
+#include "handoff.hpp"
+#include "level2_common.hpp"
 
 namespace omr {
 
@@ -219,6 +222,13 @@ struct Fft1024 {
 #pragma unroll
     for (int k = 0; k < 2; ++k) w[k] = twg[TW_LEN + ct_off(P) + 2 * b + k];
   }
+  // thread t's forward twiddles of passes 1..4 (wc[P - 1]), for every transform it runs
+  __device__ static __forceinline__ void load_ct(double2 (&wc)[4][2], const double2 *__restrict__ twg, int t) {
+    block_ct<1>(wc[0], twg, t);
+    block_ct<2>(wc[1], twg, t);
+    block_ct<3>(wc[2], twg, t);
+    block_ct<4>(wc[3], twg, t);
+  }
   // forward: in P0 layout (point idx(0, t, e)), out P4 layout. X: this transform's cross-wave buffer;
   // the wave-local exchange (P3 -> P4) runs in the wave's own quarter of X (slot bits 9, 8 = wave:
   // tests/test_fft2_layout.py::test_exchange_regions), which after this transform's cross-wave reads
@@ -332,17 +342,42 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t bsk2_rsrc(const double2 *bskf)
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<double2 *>(bskf), 0, bytes, 0x00020000);
 }
 typedef unsigned br2_v4u __attribute__((ext_vector_type(4)));
-// output o's two limb blocks of global row q: thread t's 4 points (key_pos(t, e) = e * 256 + t)
+// the block of output o, limb l of global row q: thread t's 4 points (key_pos(t, e) = e * 256 + t)
+__device__ __forceinline__ void br2f_load_block(double2 (&k)[Fft1024::E], __amdgpu_buffer_rsrc_t rsrc, int q, int o,
+                                                int l, uint32_t t16) {
+#pragma unroll
+  for (int e = 0; e < Fft1024::E; ++e) {
+    const uint32_t soff = (uint32_t)q * (uint32_t)(BR2_ROW * sizeof(double2)) +
+                          (uint32_t)(((o * 2 + l) * Fft1024::n + e * Fft1024::T) * sizeof(double2));
+    k[e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, t16, (int)soff, 0));
+  }
+}
+// output o's two limb blocks
 __device__ __forceinline__ void br2f_load_half(double2 (&k)[2][Fft1024::E], __amdgpu_buffer_rsrc_t rsrc, int q,
                                                int o, uint32_t t16) {
+  br2f_load_block(k[0], rsrc, q, o, 0, t16);
+  br2f_load_block(k[1], rsrc, q, o, 1, t16);
+}
+// A transformed digit (xr, xi) times one output's two limb blocks k, into that output's spectra
+__device__ __forceinline__ void br2f_mac(const double (&xr)[Fft1024::E], const double (&xi)[Fft1024::E],
+                                         const double2 (&k)[2][Fft1024::E], double (&sr)[2][Fft1024::E],
+                                         double (&si)[2][Fft1024::E]) {
 #pragma unroll
   for (int l = 0; l < 2; ++l)
 #pragma unroll
     for (int e = 0; e < Fft1024::E; ++e) {
-      const uint32_t soff = (uint32_t)q * (uint32_t)(BR2_ROW * sizeof(double2)) +
-                            (uint32_t)(((o * 2 + l) * Fft1024::n + e * Fft1024::T) * sizeof(double2));
-      k[l][e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, t16, (int)soff, 0));
+      const double2 kv = k[l][e];
+      sr[l][e] = __fma_rn(xr[e], kv.x, __fma_rn(-xi[e], kv.y, sr[l][e]));
+      si[l][e] = __fma_rn(xr[e], kv.y, __fma_rn(xi[e], kv.x, si[l][e]));
     }
+}
+__device__ __forceinline__ void br2f_zero(double (&sr)[2][2][Fft1024::E], double (&si)[2][2][Fft1024::E]) {
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int l = 0; l < 2; ++l)
+#pragma unroll
+      for (int e = 0; e < Fft1024::E; ++e) sr[o][l][e] = si[o][l][e] = 0.0;
 }
 
 // Digit words of (X^a - 1) * ACC_p from the LDS-resident accumulator (acp: 2048 doubles at
@@ -390,14 +425,6 @@ __device__ __forceinline__ void br2f_digit(const uint32_t (&pk)[2][Fft1024::E][D
   // output B's limb-0 blocks issued mid-transform (after its cross-wave exchange: 1.3 % faster at
   // level 2 than after the transform; both limbs there spill and run 20-34 % slower,
   // profiles/r05zf/bench_variants.log), limb 1 after it, in flight across output A's products
-  auto load_kb = [&](int l) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const uint32_t soff = (uint32_t)q * (uint32_t)(BR2_ROW * sizeof(double2)) +
-                            (uint32_t)(((1 * 2 + l) * Fft1024::n + e * Fft1024::T) * sizeof(double2));
-      kb[l][e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, t16, (int)soff, 0));
-    }
-  };
   // Wave priority (s_setprio) raised from the transform's cross-wave barrier to the end of the
   // digit's multiply-accumulates, normal otherwise: of the two workgroups sharing each SIMD, the wave
   // past a barrier issues first, so a workgroup's four waves reach the next barrier closer together
@@ -409,20 +436,13 @@ __device__ __forceinline__ void br2f_digit(const uint32_t (&pk)[2][Fft1024::E][D
   F::fwd(xr, xi, X, t, wc, [&]() {
     __builtin_amdgcn_s_setprio(2);
 #pragma unroll
-    for (int l = 0; l < LE; ++l) load_kb(l);
+    for (int l = 0; l < LE; ++l) br2f_load_block(kb[l], rsrc, q, 1, l, t16);
   });
 #pragma unroll
-  for (int l = LE; l < 2; ++l) load_kb(l);
+  for (int l = LE; l < 2; ++l) br2f_load_block(kb[l], rsrc, q, 1, l, t16);
 #pragma unroll
-  for (int o = 0; o < 2; ++o) {
-#pragma unroll
-    for (int l = 0; l < 2; ++l)
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const double2 kv = o ? kb[l][e] : ka[l][e];
-        sr[o][l][e] = __fma_rn(xr[e], kv.x, __fma_rn(-xi[e], kv.y, sr[o][l][e]));
-        si[o][l][e] = __fma_rn(xr[e], kv.y, __fma_rn(xi[e], kv.x, si[o][l][e]));
-      }
+  for (int o = 0; o < 2; ++o) {  // (as a loop: two calls in a row spill 9 VGPRs here)
+    br2f_mac(xr, xi, o ? kb : ka, sr[o], si[o]);
     if (o == 0) br2f_load_half(ka, rsrc, nx, 0, t16);
   }
   __builtin_amdgcn_s_setprio(0);
@@ -447,6 +467,21 @@ __device__ __forceinline__ void br2f_update(double *aco, const double (&sr)[2][F
     }
 }
 
+// LDS of br2f_body and trace_fft_body, carved from one 80 KB pool (two workgroups per CU): X0, X1
+// (the transforms' cross-wave buffers), ACC (mask, body at slot_stage positions), then the twiddles.
+constexpr size_t BR2_LDS_X = 0, BR2_LDS_TWS = 4 * (size_t)Fft1024::n * sizeof(double2),
+                 BR2_LDS_BYTES = BR2_LDS_TWS + (size_t)Fft1024::n * sizeof(double2);
+struct Br2Lds {
+  double2 *tws;
+  double2 (*Xb)[Fft1024::n];  // X0, X1
+  double *acs;
+};
+__device__ __forceinline__ Br2Lds br2_lds(double2 *pool) {
+  double2 *x = pool + BR2_LDS_X / sizeof(double2);
+  return {pool + BR2_LDS_TWS / sizeof(double2), reinterpret_cast<double2(*)[Fft1024::n]>(x),
+          reinterpret_cast<double *>(x + 2 * Fft1024::n)};
+}
+
 // hom_trace (detector.rs:626-639; secret.rs:167-168 for N^-1) on the exact FFT (round 5), in place on
 // the LDS-resident accumulator (acs: mask, body at slot_stage positions, canonical): c *= N^-1, then
 // for each of the 11 automorphisms sigma_g: c += KS_g(sigma_g(c)), where the key switch decomposes
@@ -461,18 +496,17 @@ __device__ __forceinline__ void br2f_update(double *aco, const double (&sr)[2][F
 // NTT trace when it is not below 0.5. 25 transforms of 120 FP64 operations per thread and step
 // instead of 25 modular NTTs of ~450.
 template <bool G>
-__device__ __forceinline__ void br2f_trace(double *acs, const double2 *__restrict__ tkf, double2 (&Xb)[2][Fft1024::n],
-                                           const double2 *tws, const double2 *__restrict__ twg, const DeviceTables &tb,
+__device__ __forceinline__ void br2f_trace(const Br2Lds &lds, const double2 *__restrict__ tkf,
+                                           const double2 *__restrict__ twg, const DeviceTables &tb,
                                            RoundGuard<G> &rg, int t) {
   using F = Fft1024;
   using M = Mod<2>;
   constexpr int E = F::E, NN = N2;
+  double *acs = lds.acs;
+  double2(*Xb)[F::n] = lds.Xb;
+  const double2 *tws = lds.tws;
   double2 wc[4][2];  // the forward twiddles again (not kept live across the rotation)
-  F::block_ct<1>(wc[0], twg, t);
-  F::block_ct<2>(wc[1], twg, t);
-  F::block_ct<3>(wc[2], twg, t);
-  F::block_ct<4>(wc[3], twg, t);
-  constexpr double NINV = -549755813880.0;  // 2048^-1 mod q2 = 1125350151012361, centred
+  F::load_ct(wc, twg, t);
   static_assert(DT == 25 && TRACE_STEPS == 11, "trace geometry");
 #pragma unroll
   for (int p = 0; p < 2; ++p)
@@ -481,7 +515,7 @@ __device__ __forceinline__ void br2f_trace(double *acs, const double2 *__restric
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         double &x = acs[p * NN + F::slot_stage(F::idx(0, t, e) + F::n * h)];
-        x = canon<M>(mm<M>(x, NINV));
+        x = canon<M>(mm<M>(x, NINV2));
       }
   constexpr uint32_t bytes = (uint32_t)((size_t)TRACE_STEPS * DT * BR2_ROW * sizeof(double2));
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double2 *>(tkf), 0, bytes, 0x00020000);
@@ -503,12 +537,7 @@ __device__ __forceinline__ void br2f_trace(double *acs, const double2 *__restric
         asm volatile("" : "+v"(pk[h][e][0]), "+v"(pk[h][e][1]));
       }
     double sr[2][2][E], si[2][2][E];  // [output A / B][limb]
-#pragma unroll
-    for (int o = 0; o < 2; ++o)
-#pragma unroll
-      for (int l = 0; l < 2; ++l)
-#pragma unroll
-        for (int e = 0; e < E; ++e) sr[o][l][e] = si[o][l][e] = 0.0;
+    br2f_zero(sr, si);
 #pragma unroll 1
     for (int d = 0; d < DT; ++d) {
       const int q = k * DT + d;
@@ -519,26 +548,11 @@ __device__ __forceinline__ void br2f_trace(double *acs, const double2 *__restric
         xi[e] = DigitsTrace::get(pk[1][e], d);
       }
       // output B's limb-0 blocks mid-transform, limb 1 after it (as br2f_digit)
-      auto load_kb = [&](int l) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const uint32_t soff = (uint32_t)q * (uint32_t)(BR2_ROW * sizeof(double2)) +
-                                (uint32_t)(((1 * 2 + l) * Fft1024::n + e * Fft1024::T) * sizeof(double2));
-          kb[l][e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, t16, (int)soff, 0));
-        }
-      };
-      F::fwd(xr, xi, Xb[d & 1], t, wc, [&]() { load_kb(0); });
-      load_kb(1);
+      F::fwd(xr, xi, Xb[d & 1], t, wc, [&]() { br2f_load_block(kb[0], rsrc, q, 1, 0, t16); });
+      br2f_load_block(kb[1], rsrc, q, 1, 1, t16);
 #pragma unroll
       for (int o = 0; o < 2; ++o) {
-#pragma unroll
-        for (int l = 0; l < 2; ++l)
-#pragma unroll
-          for (int e = 0; e < E; ++e) {
-            const double2 kv = o ? kb[l][e] : ka[l][e];
-            sr[o][l][e] = __fma_rn(xr[e], kv.x, __fma_rn(-xi[e], kv.y, sr[o][l][e]));
-            si[o][l][e] = __fma_rn(xr[e], kv.y, __fma_rn(xi[e], kv.x, si[o][l][e]));
-          }
+        br2f_mac(xr, xi, o ? kb : ka, sr[o], si[o]);
         if (o == 0) br2f_load_half(ka, rsrc, d + 1 < DT ? q + 1 : q, 0, t16);
       }
     }
@@ -590,11 +604,6 @@ __device__ __forceinline__ void br2f_trace(double *acs, const double2 *__restric
 // use rewrites a buffer whose readers have passed a later barrier: 17 workgroup barriers per step
 // (one at the step start: the previous update visible to the rotated reads).
 // LDS: twiddles 16 KB, X0 / X1 32 KB, ACC 32 KB (80 KB: two workgroups per CU).
-// LDS of br2f_body, carved from one pool: the twiddles,
-// then X0, X1, ACC (mask, body); the trace's 3 N2 doubles afterwards: 80 KB.
-constexpr size_t BR2_LDS_X = 0, BR2_LDS_TWS = 4 * (size_t)Fft1024::n * sizeof(double2),
-                 BR2_LDS_BYTES = BR2_LDS_TWS + (size_t)Fft1024::n * sizeof(double2);
-
 template <bool G>
 __device__ __forceinline__ void br2f_body(const uint32_t *__restrict__ lwe_int, const double2 *__restrict__ bskf,
                                           const double2 *__restrict__ twg, DeviceTables tb, uint64_t *__restrict__ out,
@@ -603,31 +612,27 @@ __device__ __forceinline__ void br2f_body(const uint32_t *__restrict__ lwe_int, 
   using M = Mod<2>;
   constexpr int E = F::E, NN = N2;
   static_assert(F::TW_LEN <= F::n, "the twiddle table's LDS doubles as the trace's NTT table");
-  double2 *tws = pool + BR2_LDS_TWS / sizeof(double2);
-  double2(&lds)[4][F::n] = *reinterpret_cast<double2(*)[4][F::n]>(pool + BR2_LDS_X / sizeof(double2));
-  double2(&Xb)[2][F::n] = *reinterpret_cast<double2(*)[2][F::n]>(&lds[0][0]);
-  double *acs = reinterpret_cast<double *>(&lds[2][0]);
+  const Br2Lds lds = br2_lds(pool);
+  double2 *tws = lds.tws;
+  double2(*Xb)[F::n] = lds.Xb;
+  double *acs = lds.acs;
   const int t = threadIdx.x;
   const uint32_t *lwe = lwe_int + item * (NI + 1);
   F::load_twiddles(tws, twg, t);
   {  // ACC = (0, X^{-b} * LUT2)
     const int b = (int)lwe[NI];
-    const int rr = (2 * NN - (b % (2 * NN))) % (2 * NN);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int c = F::idx(0, t, e) + F::n * h;
         acs[F::slot_stage(c)] = 0.0;
-        acs[NN + F::slot_stage(c)] = canon_small<M>(rot_read<NN>(tb.lut2, c, rr));
+        acs[NN + F::slot_stage(c)] = acc2_init(tb.lut2, b, c);
       }
   }
   __syncthreads();
   double2 wc[4][2];  // this thread's forward twiddles of passes 1..4, for every transform of the rotation
-  F::block_ct<1>(wc[0], twg, t);
-  F::block_ct<2>(wc[1], twg, t);
-  F::block_ct<3>(wc[2], twg, t);
-  F::block_ct<4>(wc[3], twg, t);
+  F::load_ct(wc, twg, t);
   double2 ka[2][E], kb[2][E];
   const __amdgpu_buffer_rsrc_t rsrc = bsk2_rsrc(bskf);
   const uint32_t t16 = (uint32_t)t * 16u;
@@ -655,14 +660,7 @@ __device__ __forceinline__ void br2f_body(const uint32_t *__restrict__ lwe_int, 
         return q0 + (w == 0 ? p * D2 + j + 3
                             : (j + 1 < D2 / 2 ? p * D2 + j + 1 : (p == 0 ? D2 : (kq >= 0 ? 2 * D2 : 2 * D2 - 1))));
       };
-      if (p == 0) {  // (peeling the step's first digit instead measured 10 % slower: 22 spills)
-#pragma unroll
-        for (int o = 0; o < 2; ++o)
-#pragma unroll
-          for (int l = 0; l < 2; ++l)
-#pragma unroll
-            for (int e = 0; e < E; ++e) sr[o][l][e] = si[o][l][e] = 0.0;
-      }
+      if (p == 0) br2f_zero(sr, si);  // (peeling the step's first digit instead measured 10 % slower: 22 spills)
 #pragma unroll 1
       for (int j = 0; j < D2 / 2; ++j) {
         br2f_digit<0>(pk, j, q0 + p * D2 + j, nxt(j, 0), sr, si, ka, kb, Xb[0], rsrc, t16, t, wc);
@@ -707,10 +705,9 @@ __device__ __forceinline__ void trace_fft_body(uint64_t *__restrict__ io, const 
   using M = Mod<2>;
   constexpr int E = F::E, NN = N2;
   __shared__ double2 pool[BR2_LDS_BYTES / sizeof(double2)];
-  double2 *tws = pool + BR2_LDS_TWS / sizeof(double2);
-  double2(&lds)[4][F::n] = *reinterpret_cast<double2(*)[4][F::n]>(pool + BR2_LDS_X / sizeof(double2));
-  double2(&Xb)[2][F::n] = *reinterpret_cast<double2(*)[2][F::n]>(&lds[0][0]);
-  double *acs = reinterpret_cast<double *>(&lds[2][0]);
+  const Br2Lds lds = br2_lds(pool);
+  double2 *tws = lds.tws;
+  double *acs = lds.acs;
   const int t = threadIdx.x;
   uint64_t *o = io + (size_t)blockIdx.x * 2 * NN;
   F::load_twiddles(tws, twg, t);
@@ -724,7 +721,7 @@ __device__ __forceinline__ void trace_fft_body(uint64_t *__restrict__ io, const 
         acs[p * NN + F::slot_stage(c)] = from_u64<M>(o[p * NN + c]);
       }
   RoundGuard<G> rg;
-  br2f_trace<G>(acs, tkf, Xb, tws, twg, tb, rg, t);
+  br2f_trace<G>(lds, tkf, twg, tb, rg, t);
   rg.publish(margin);
   __syncthreads();  // the last updates everywhere
   // to_ntt_rlwe: both halves to the NTT domain (the trace NTTs' coefficient layout t + 256 e)
@@ -735,7 +732,7 @@ __device__ __forceinline__ void trace_fft_body(uint64_t *__restrict__ io, const 
     ca[e] = acs[F::slot_stage(t + e * BR2_T)];
     cb[e] = acs[NN + F::slot_stage(t + e * BR2_T)];
   }
-  double *xch = reinterpret_cast<double *>(&lds[0][0]);  // 2 N2 doubles (below the accumulator)
+  double *xch = reinterpret_cast<double *>(lds.Xb);  // 2 N2 doubles (below the accumulator)
   double *tw = reinterpret_cast<double *>(tws);           // N2 doubles
   static_assert(NTT::LDS_DOUBLES * sizeof(double) <= 2 * F::n * sizeof(double2), "NTT exchange below ACC");
 #pragma unroll
@@ -778,7 +775,7 @@ __global__ __launch_bounds__(256, 2) void br2f_guard_kernel(const uint32_t *__re
 
 
 // ---- level 2 over two CUs per message on the exact FFT (the latency path) --------------------
-// br2x_kernel's division of labour (latency_kernels.hpp) on br2f's arithmetic. Workgroup 2m + r
+// br2x_kernel's division of labour (br2_ntt.hpp) on br2f's arithmetic. Workgroup 2m + r
 // owns polynomial r (0 mask, 1 body) of message m and its accumulator ACC_r (LDS, slot_stage
 // positions). Its group g (256 threads: one Fft1024 transform) takes word g of the Digits2S
 // decomposition of (X^a - 1) ACC_r -- digits 3g + j, GGSW rows r D2 + 3g + j -- and for each digit
@@ -892,9 +889,7 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
   if (g == 0) F::load_twiddles(tws, twg, t);
   {  // ACC_r = X^{-b} * LUT2 (body) or 0 (mask)
     const int b = (int)lwe[NI];
-    const int rr = (2 * NN - (b % (2 * NN))) % (2 * NN);
-    for (int c = (int)threadIdx.x; c < NN; c += BR2Y_T)
-      acs[F::slot_stage(c)] = r == 1 ? canon_small<M>(rot_read<NN>(tb.lut2, c, rr)) : 0.0;
+    for (int c = (int)threadIdx.x; c < NN; c += BR2Y_T) acs[F::slot_stage(c)] = r == 1 ? acc2_init(tb.lut2, b, c) : 0.0;
     if (threadIdx.x == 0) {
       stop = 0;
       // XCD ids through global memory (sc1 both ways); a partner that never answers leaves the
@@ -911,15 +906,11 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
     }
   }
   double2 wc[4][2];  // this thread's forward twiddles of passes 1..4
-  F::block_ct<1>(wc[0], twg, t);
-  F::block_ct<2>(wc[1], twg, t);
-  F::block_ct<3>(wc[2], twg, t);
-  F::block_ct<4>(wc[3], twg, t);
+  F::load_ct(wc, twg, t);
   __syncthreads();  // same_xcd (and the accumulator) visible
   const bool fast = __builtin_amdgcn_readfirstlane(same_xcd) != 0;
   const __amdgpu_buffer_rsrc_t rsrc = bsk2_rsrc(bskf);
   const uint32_t t16 = (uint32_t)t * 16u;
-  uint32_t *my_flag = flags + 2 * m + r, *their_flag = flags + 2 * m + (1 - r);
   uint32_t hc = 0;  // hand-offs so far (executed steps)
   double2 ka[2][E], kb[2][E];
   int pre = -1;  // the step whose first row ka / kb hold
@@ -945,12 +936,7 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
     }
     OMR_PHASE(pslot, (int)hc, 1);
     double sr[2][2][E], si[2][2][E];  // [output][limb] partial spectra of the group's three digits
-#pragma unroll
-    for (int o = 0; o < 2; ++o)
-#pragma unroll
-      for (int l = 0; l < 2; ++l)
-#pragma unroll
-        for (int e = 0; e < E; ++e) sr[o][l][e] = si[o][l][e] = 0.0;
+    br2f_zero(sr, si);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int wd = g == 1 && j == 2 ? Digits2S::TOP_WIDTH : 7;  // the top digit of word 1
@@ -963,20 +949,8 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
       F::fwd(xr, xi, xb[g][j & 1], t, wc);
 #pragma unroll
       for (int o = 0; o < 2; ++o) {
-#pragma unroll
-        for (int l = 0; l < 2; ++l)
-#pragma unroll
-          for (int e = 0; e < E; ++e) {
-            const double2 kv = o ? kb[l][e] : ka[l][e];
-            sr[o][l][e] = __fma_rn(xr[e], kv.x, __fma_rn(-xi[e], kv.y, sr[o][l][e]));
-            si[o][l][e] = __fma_rn(xr[e], kv.y, __fma_rn(xi[e], kv.x, si[o][l][e]));
-          }
-        if (j < 2) {
-          if (o == 0)
-            br2f_load_half(ka, rsrc, q0 + j + 1, 0, t16);
-          else
-            br2f_load_half(kb, rsrc, q0 + j + 1, 1, t16);
-        }
+        br2f_mac(xr, xi, o ? kb : ka, sr[o], si[o]);
+        if (j < 2) br2f_load_half(o ? kb : ka, rsrc, q0 + j + 1, o, t16);
       }
     }
     OMR_PHASE(pslot, (int)hc, 2);
@@ -1014,8 +988,7 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
     double fr[E], fi[E];  // limb g of output r: this workgroup's six rows, then the partner's six
     {
       const double2 *qr = xb[1 - g][1], *qh = px[1 - g];
-      const size_t slot = hc & 1;
-      double *dst = xg + ((((size_t)m * 2 + r) * 2 + slot) * 2 + g) * 2 * n;
+      double *dst = br2y_slot(xg, m, r, hc & 1, g);
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const double2 vr = qr[e * T + t], vh = qh[e * T + t];
@@ -1033,26 +1006,12 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
     }
     __syncthreads();
     OMR_PHASE(pslot, (int)hc, 4);
-    if (threadIdx.x == 0) {
-      if (fast)
-        __hip_atomic_store(my_flag, hc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // plain store
-      else
-        __hip_atomic_store(my_flag, hc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      int k = 0;
-      while (__hip_atomic_load(their_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < hc + 1) {
-        if (++k == BR2X_SPIN) {
-          stop = 1;
-          atomicExch(err, 1);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
+    if (threadIdx.x == 0) handoff_flags(flags + 2 * m, 2, r, hc + 1, fast, &stop, err);  // fast: a plain flag store
     __syncthreads();
     OMR_PHASE(pslot, (int)hc, 5);
     if (stop) break;
     {  // the partner's limb g of output r
-      const double *src = xg + ((((size_t)m * 2 + (1 - r)) * 2 + (hc & 1)) * 2 + g) * 2 * n;
+      const double *src = br2y_slot(xg, m, 1 - r, hc & 1, g);
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         fr[e] += ld_sc1(src + e * T + t);

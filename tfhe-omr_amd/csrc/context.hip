@@ -21,14 +21,15 @@
 #include <string>
 #include <vector>
 
+#include "br1_latency.hpp"
 #include "br1_ntt.hpp"
 #include "br2_fft.hpp"
-#include "detect_kernels.hpp"
+#include "br2_ntt.hpp"
 #include "encode_kernels.hpp"
 #include "hip_util.hpp"
 #include "host_tables.hpp"
 #include "key_spectra.hpp"
-#include "latency_kernels.hpp"
+#include "ks_mfma.hpp"
 
 using namespace omr;
 #ifndef OMR_DEFAULT_LATENCY_MAX
@@ -58,18 +59,18 @@ struct omr_ctx {
   size_t batch = OMR_DEFAULT_BATCH;
   size_t enc_max_chunks = OMR_ENC_MAX_CHUNKS;  // chunk partials per encode ciphertext (omr_ctx_set_encode_chunks)
   DevBuf<uint32_t> ext, lwe1t, lwe_int;  // per-chunk scratch, grown together (ensure_batch)
-  // chunks of at most latency_max messages run the latency kernels (latency_kernels.hpp)
+  // chunks of at most latency_max messages run the latency kernels (br1_latency.hpp)
   size_t latency_max = OMR_DEFAULT_LATENCY_MAX;
   DevBuf<int> ks_part;  // split key-switch partial sums, [KS_SPLIT][64][672][4]
-  // two-CU level-2 latency kernel (br2x_kernel, cooperative launch): partial hand-off slots
-  // [n][2][2][N2], flags [n][2], a timeout flag x_err that every launch copies to the pinned host
-  // word x_err_host on its stream (read by omr_ctx_check and at the start of the next call)
+  // two-CU level-2 latency kernels (br2x_kernel, br2y_kernel; cooperative launch): hand-off slots
+  // and flags (handoff.hpp: BR2XY_SLOT_DOUBLES, BR2XY_FLAGS per message), a timeout flag x_err that
+  // every launch copies to the pinned host word x_err_host on its stream (read by omr_ctx_check
+  // and at the start of the next call)
   DevBuf<double> x_slots;
   DevBuf<uint32_t> x_flags;
   DevBuf<int> x_err;
   int *x_err_host = nullptr;
-  // multi-CU trace of the latency path (trace_x_kernel): partial slots [n][TRACE_X][2][2][N2],
-  // flags [n][TRACE_X]
+  // multi-CU trace of the latency path (trace_x_kernel): TRACE_X_SLOT_DOUBLES, TRACE_X_FLAGS per message
   DevBuf<double> t_slots;
   DevBuf<uint32_t> t_flags;
   int num_cu = 0;
@@ -402,8 +403,8 @@ omr_status launch_br2x(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t *
   *launched = false;
   if (!c->coop || 2 * n > (size_t)c->num_cu) return OMR_OK;  // one 150 KB-LDS workgroup per CU
   omr_status s;
-  // br2y: slots [n][2][2 slot][2 limb][2][1024], flags + the workers' XCD ids
-  if ((s = handoff_scratch(c, c->x_slots, n * 8 * N2, c->x_flags, n * 4, st)) != OMR_OK) return s;
+  // sized for whichever of br2x / br2y runs (handoff.hpp)
+  if ((s = handoff_scratch(c, c->x_slots, n * BR2XY_SLOT_DOUBLES, c->x_flags, n * BR2XY_FLAGS, st)) != OMR_OK) return s;
   const double *bsk2 = c->bsk2;
   DeviceTables tb = c->tb;
   double *slots = c->x_slots;
@@ -434,7 +435,7 @@ omr_status launch_trace_x(omr_ctx *c, size_t n, uint64_t *io, hipStream_t st, bo
   *launched = false;
   if (!c->coop || TRACE_X * n > 2 * (size_t)c->num_cu) return OMR_OK;
   omr_status s;
-  if ((s = handoff_scratch(c, c->t_slots, n * TRACE_X * 4 * N2, c->t_flags, n * TRACE_X, st)) != OMR_OK) return s;
+  if ((s = handoff_scratch(c, c->t_slots, n * TRACE_X_SLOT_DOUBLES, c->t_flags, n * TRACE_X_FLAGS, st)) != OMR_OK) return s;
   const double *tk = c->tk;
   DeviceTables tb = c->tb;
   double *slots = c->t_slots;

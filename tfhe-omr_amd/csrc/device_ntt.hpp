@@ -495,7 +495,7 @@ struct CmuxNtt {
   }
   // Two unscaled inverses interleaved (the CMUX step's outputs A and B) for instruction-level
   // parallelism: the wave-local exchanges run one after the other through W; the cross-wave
-  // exchanges keep cmux_step3's order and barriers (A through X1, then B through X0: X0 is written
+  // exchanges keep the digit transforms' order and barriers (A through X1, then B through X0: X0 is written
   // only after a barrier that every wave passes after its last X0 read of the body digits).
   __device__ static __forceinline__ void inv2(double (&xa)[E], double (&xb)[E], double *lds, const double *tw,
                                               int tid, const double *__restrict__ gt) {

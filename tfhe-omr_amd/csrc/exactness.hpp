@@ -1,7 +1,7 @@
 // Exactness of the FFT external products ("Worst-case error bound").
 //
 // Both throughput blind rotations (br1_fft.hpp, br2_fft.hpp) and the latency level 1
-// (latency_kernels.hpp) compute sum_r digit_r * key_r with FP64 complex FFTs and round the
+// (br1_latency.hpp) compute sum_r digit_r * key_r with FP64 complex FFTs and round the
 // result to the integer it equals. This header holds the three pieces that make that rounding
 // provably exact rather than empirically so:
 //  - key spectra in double-double: the keys are transformed once, at context creation, by a
@@ -151,6 +151,11 @@ __global__ void guard_fold_kernel(unsigned long long *words, int level, double t
   const unsigned long long m = words[2 + level];
   atomicMax(&words[level], m);
   if (__longlong_as_double((long long)m) >= thr) atomicAdd(&words[4 + level], 1ull);
+}
+// What every workgroup of an exact fallback kernel asks first: did the guarded launch's observed
+// rounding margin reach the certificate threshold 1 - E? (It leaves at once otherwise.)
+__device__ __forceinline__ bool margin_breached(const unsigned long long *word, double thr) {
+  return __longlong_as_double((long long)*word) >= thr;
 }
 
 }  // namespace omr

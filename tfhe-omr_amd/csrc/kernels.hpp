@@ -25,6 +25,22 @@ struct DeviceTables {
   const double2 *fft1;                    // level-1 FFT twiddles
 };
 
+// (X^r * p)[j] for p in LDS, r in [0, 2N): sign-corrected read.
+template <int N>
+__device__ __forceinline__ double rot_read(const double *p, int j, int r) {
+  int t = j - r;
+  double s = 1.0;
+  if (t < 0) {
+    t += N;
+    s = -1.0;
+  }
+  if (t < 0) {
+    t += N;
+    s = 1.0;
+  }
+  return s * p[t];
+}
+
 // ---- key conversion: coefficient-domain canonical residues -> NTT-domain centred residues ----
 template <int LEVEL, typename IN, typename OUT>
 __global__ void key_to_ntt_kernel(const IN *in, OUT *out, size_t npoly, double scale,

@@ -105,4 +105,77 @@ __global__ __launch_bounds__(64, 2) void ks_mfma_kernel(const uint32_t *__restri
     }
 }
 
+// Sum of the 7 extracted LWEs mod q1 (detector.rs:556), transposed to [N1+1][B] for the key
+// switch (lanes = messages).
+__global__ void sum7_kernel(const uint32_t *__restrict__ ext, uint32_t *__restrict__ lwe1t,
+                            int B) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)B * (N1 + 1)) return;
+  const size_t m = idx % B, i = idx / B;
+  uint32_t s = 0;
+#pragma unroll
+  for (int c = 0; c < CLUES; ++c) s += ext[(m * CLUES + c) * (N1 + 1) + i];
+  lwe1t[i * B + m] = s % (uint32_t)Q1;
+}
+
+// ---- key switch, split over the input coefficients (the latency path: a lone message otherwise
+// gets 21 waves for 88 MB of KSK) ------------------------------------------------------------------
+constexpr int KS_SPLIT = 32;  // slices of the 1024 input coefficients
+
+// grid (ceil(B / 64), 21, KS_SPLIT): ks_mfma_kernel's tile over input coefficients
+// [z * 1024 / KS_SPLIT, (z + 1) * 1024 / KS_SPLIT); int32 limb sums to part[z][m][col][limb].
+__global__ __launch_bounds__(64, 2) void ks_mfma_split_kernel(const uint32_t *__restrict__ lwe1t,
+                                                           const uint32_t *__restrict__ kskb,
+                                                           int *__restrict__ part, int B, int Bpad) {
+  const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+  const int m0 = blockIdx.x * 64, c0 = blockIdx.y * 32, z = blockIdx.z;
+  omr_v16i acc[2][KSM_LIMBS];
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+    for (int l = 0; l < KSM_LIMBS; ++l) acc[tt][l] = omr_v16i{};
+  const bool live0 = m0 + r < B, live1 = m0 + 32 + r < B;
+  const omr_v4i *bbase = reinterpret_cast<const omr_v4i *>(kskb) + (size_t)(c0 + r) * 2 + h;
+  constexpr int SL = N1 / KS_SPLIT;
+#pragma unroll 1
+  for (int i = z * SL; i < (z + 1) * SL; ++i) {
+    const uint32_t x0 = live0 ? lwe1t[(size_t)i * B + m0 + r] : 0u;
+    const uint32_t x1 = live1 ? lwe1t[(size_t)i * B + m0 + 32 + r] : 0u;
+    const omr_v4i a0 = bit_bytes16(x0, 16 * h), a1 = bit_bytes16(x1, 16 * h);
+#pragma unroll
+    for (int l = 0; l < KSM_LIMBS; ++l) {
+      const omr_v4i bv = bbase[((size_t)i * KSM_LIMBS + l) * KSM_COLS * 2];
+      acc[0][l] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, bv, acc[0][l], 0, 0, 0);
+      acc[1][l] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, bv, acc[1][l], 0, 0, 0);
+    }
+  }
+  const int col = c0 + r;
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int m = m0 + 32 * tt + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+      int *p = part + (((size_t)z * Bpad + m) * KSM_COLS + col) * KSM_LIMBS;
+#pragma unroll
+      for (int l = 0; l < KSM_LIMBS; ++l) p[l] = acc[tt][l][reg];
+    }
+}
+
+// Sum of the slices and ks_mfma_kernel's epilogue: one thread per (message, output column).
+__global__ void ks_combine_kernel(const int *__restrict__ part, const uint32_t *__restrict__ lwe1t,
+                                  uint32_t *__restrict__ lwe_int, int B, int Bpad) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * (NI + 1)) return;
+  const int m = idx / (NI + 1), col = idx % (NI + 1);
+  int64_t limb[KSM_LIMBS] = {0, 0, 0, 0};
+  for (int z = 0; z < KS_SPLIT; ++z) {
+    const int *p = part + (((size_t)z * Bpad + m) * KSM_COLS + col) * KSM_LIMBS;
+#pragma unroll
+    for (int l = 0; l < KSM_LIMBS; ++l) limb[l] += p[l];
+  }
+  const uint64_t sum = (uint64_t)limb[0] + ((uint64_t)limb[1] << 7) + ((uint64_t)limb[2] << 14) +
+                       ((uint64_t)limb[3] << 21);
+  lwe_int[(size_t)m * (NI + 1) + col] = ks_epilogue(sum, lwe1t[(size_t)N1 * B + m], col);
+}
+
 }  // namespace omr
