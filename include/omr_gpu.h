@@ -304,6 +304,78 @@ omr_status omr_encode_payloads_device(omr_ctx *ctx, const uint64_t *d_pv,
                                       void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Digest session — the detector's whole board flow (examples/omr.rs:160-203: detect every message,
+ * encode_pertinent_indices per index ciphertext, encode_pertinent_payloads once; detector.rs:223-453)
+ * behind one handle that never holds the board's pertinency vector. The caller feeds message
+ * ranges in any order and any sizes; the library detects and encodes them in pieces of at most the
+ * context's detect batch (omr_ctx_set_batch) and keeps the running digest, the ciphertexts that
+ * Retriever::decode_digest (retriever.rs:188-260) consumes, on the device. The digest is an exact
+ * sum mod q2 of per-message terms, so every partition of a board into updates, and every split of
+ * it over sessions joined by omr_digest_merge, gives the same bits as omr_detect_batch followed by
+ * omr_encode_indices for each ciphertext and omr_encode_payloads.
+ *
+ * Calls on one session are serialised. Several sessions may live on one context and interleave
+ * with any other call on it: each session owns its buffers and shares the context's detect / encode
+ * scratch in stream order like every device entry point. Destroying the context before its
+ * sessions is a caller error (a session uses the context until omr_digest_destroy returns).
+ * ------------------------------------------------------------------------------------- */
+typedef struct omr_digest omr_digest;
+
+typedef struct {
+  uint32_t index_ct, payload_ct;      /* rp.max_encode_indices_cipher_count, rp.cmb_cipher_count */
+  uint32_t combination_count, cmb_count_per_cipher;
+  size_t   all_payloads_count;
+  size_t   messages;                  /* global indices folded in by update calls of THIS session */
+  size_t   pv_capacity_messages;      /* pertinency ciphertexts the session currently has room for */
+} omr_digest_info;
+
+/* A session for an all_payloads_count board: the layout is omr_get_retrieval_params(all, pertinent),
+ * the buckets of the index ciphertexts come from index_seed as in omr_encode_indices, and the weights
+ * are omr_payload_weights(weight_seed, all, combination_count, cmb_cipher_count,
+ * cmb_count_per_cipher), generated on the host and uploaded once: the call blocks while it does so.
+ * All device work of the session is enqueued on `hip_stream` (NULL = HIP's null stream). Device
+ * footprint: payload_ct * cmb_count_per_cipher * all * 2 bytes of weights, the running digest
+ * ([index_ct + payload_ct][2][2048] u64, zeroed), at most one detect chunk of pertinency
+ * ciphertexts (32 KiB per message, allocated by the first update) and, for host updates, the
+ * staging of one chunk of clues and payloads (2.3 KiB per message). */
+omr_status omr_digest_begin(omr_ctx *ctx, size_t all_payloads_count, size_t pertinent_count,
+                            uint64_t index_seed, const uint8_t weight_seed[32],
+                            void *hip_stream, omr_digest **out);
+/* Folds the messages with global indices [global_offset, global_offset + D) into the digest:
+ * clue_a u16 [D][512], clue_b u16 [D][7], payloads u16 [D][612]. Per piece of at most the context's
+ * detect batch: Detector::detect into the session's pertinency buffer, then every index ciphertext
+ * (detector.rs:223-339) and every payload ciphertext (:341-453) over it, added to the running digest
+ * mod q2. The pertinency buffer grows to min(largest piece seen, batch) messages and no further
+ * (omr_digest_info.pv_capacity_messages). OMR_ERR_INVALID_ARGUMENT, before anything is enqueued and
+ * with the session still usable, for a range that reaches beyond the board or overlaps one already
+ * folded in, or a NULL pointer with D > 0; D = 0 does nothing. Host and device updates may be mixed.
+ * Host buffers: returns once the stream has finished the update (the buffers may be reused) and
+ * reports a failed hand-off as omr_detect_batch does. Device buffers (of the context's device):
+ * returns once enqueued; the caller keeps the inputs alive and synchronises through omr_ctx_check or
+ * omr_digest_read. A device failure reported to any call on the session poisons it (see
+ * omr_digest_read). */
+omr_status omr_digest_update(omr_digest *dg, const uint16_t *clue_a, const uint16_t *clue_b,
+                             const uint16_t *payloads, size_t D, size_t global_offset);
+omr_status omr_digest_update_device(omr_digest *dg, const uint16_t *d_clue_a, const uint16_t *d_clue_b,
+                                    const uint16_t *d_payloads, size_t D, size_t global_offset);
+/* Adds another session's omr_digest_read output (host arrays; e.g. the shard of another GPU for the
+ * same board, seeds and layout) into this one mod q2, the sum the reference takes with
+ * add_element_wise (detector.rs:333-336, :445-448). Either pointer may be NULL, not both. Every value
+ * must be canonical: OMR_ERR_INVALID_ARGUMENT for one >= q2, the digest unchanged. `messages` counts
+ * this session's own updates and is not touched. Returns once the stream has taken the arrays. */
+omr_status omr_digest_merge(omr_digest *dg, const uint64_t *idx_cts, const uint64_t *pay_cts);
+/* Synchronises the session's stream and copies the canonical digest to the host: idx_cts u64
+ * [index_ct][2][2048], pay_cts u64 [payload_ct][2][2048], the inputs of omr_retrieve_indices and
+ * omr_retrieve_payloads (retriever.rs:188-260). Either pointer may be NULL. Nothing is reset, so the
+ * digest can be read between updates. A pending hand-off error of the context (omr_ctx_check) is
+ * taken here: the call then returns OMR_ERR_DEVICE and the session is poisoned, every later call on
+ * it returns OMR_ERR_DEVICE. */
+omr_status omr_digest_read(omr_digest *dg, uint64_t *idx_cts, uint64_t *pay_cts);
+omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info);
+/* Synchronises the session's stream and frees its buffers; NULL is ignored. */
+void omr_digest_destroy(omr_digest *dg);
+
+/* ---------------------------------------------------------------------------------------
  * Stage entry points (for parity tests and per-stage benchmarks, benches/two_level_bs.rs).
  * Host buffers.
  * ------------------------------------------------------------------------------------- */

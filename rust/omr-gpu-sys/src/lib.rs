@@ -7,6 +7,8 @@
 //! `encode_pertinent_payloads`), [`SecretKeyPack`] for `KeyGen::generate_secret_key` /
 //! `SecretKeyPack` (`key_gen/secret.rs:46-209`) with seeded streams, [`RetrievalParams`]
 //! (`parameters/retrieval_params.rs:50-106`) and [`Retriever`] (`retriever.rs:188-260`).
+//! [`DigestSession`] runs the whole board flow (`examples/omr.rs:160-203`) inside the library
+//! without a pertinency vector on the caller's side.
 //!
 //! Differences a caller sees, all forced by determinism across GPUs and shards: keys, clues and
 //! the bucket choices of `encode_pertinent_indices` come from seeded counter-based streams (the
@@ -55,6 +57,21 @@ pub mod ffi {
     #[repr(C)]
     pub struct OmrCtx {
         _private: [u8; 0],
+    }
+    #[repr(C)]
+    pub struct OmrDigest {
+        _private: [u8; 0],
+    }
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct OmrDigestInfo {
+        pub index_ct: u32,
+        pub payload_ct: u32,
+        pub combination_count: u32,
+        pub cmb_count_per_cipher: u32,
+        pub all_payloads_count: usize,
+        pub messages: usize,
+        pub pv_capacity_messages: usize,
     }
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -162,6 +179,19 @@ pub mod ffi {
                                           global_offset: usize, all_payloads_count: usize, d_weights: *const u16,
                                           n_ct: u32, cmb_per_ct: u32, d_out: *mut u64,
                                           hip_stream: *mut c_void) -> OmrStatus;
+
+        // digest session (examples/omr.rs:160-203 inside the library)
+        pub fn omr_digest_begin(ctx: *mut OmrCtx, all_payloads_count: usize, pertinent_count: usize,
+                                index_seed: u64, weight_seed: *const u8, hip_stream: *mut c_void,
+                                out: *mut *mut OmrDigest) -> OmrStatus;
+        pub fn omr_digest_update(dg: *mut OmrDigest, clue_a: *const u16, clue_b: *const u16, payloads: *const u16,
+                                 d: usize, global_offset: usize) -> OmrStatus;
+        pub fn omr_digest_update_device(dg: *mut OmrDigest, d_clue_a: *const u16, d_clue_b: *const u16,
+                                        d_payloads: *const u16, d: usize, global_offset: usize) -> OmrStatus;
+        pub fn omr_digest_merge(dg: *mut OmrDigest, idx_cts: *const u64, pay_cts: *const u64) -> OmrStatus;
+        pub fn omr_digest_read(dg: *mut OmrDigest, idx_cts: *mut u64, pay_cts: *mut u64) -> OmrStatus;
+        pub fn omr_digest_get_info(dg: *mut OmrDigest, info: *mut OmrDigestInfo) -> OmrStatus;
+        pub fn omr_digest_destroy(dg: *mut OmrDigest);
 
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
@@ -518,6 +548,104 @@ impl GpuDetector {
 impl Drop for GpuDetector {
     fn drop(&mut self) {
         unsafe { omr_ctx_destroy(self.ctx) }
+    }
+}
+
+/// The digest of a board: the index ciphertexts and the payload ciphertexts that
+/// `Retriever::decode_digest` takes (retriever.rs:188-260).
+pub struct Digest {
+    pub indices: Vec<NttRlwe>,
+    pub payloads: Vec<NttRlwe>,
+}
+
+/// A digest session (`omr_digest_*`): the board flow of `examples/omr.rs:160-203`, detect every
+/// message, `encode_pertinent_indices` per index ciphertext, `encode_pertinent_payloads`, run piece
+/// by piece inside the library with the running digest on the device. No pertinency vector crosses
+/// the boundary, and the library never holds more than one detect chunk of it. Message ranges may
+/// arrive in any order and any sizes; every partition gives the same digest. The borrow keeps the
+/// detector (the context) alive for as long as the session.
+pub struct DigestSession<'a> {
+    raw: *mut OmrDigest,
+    _detector: &'a GpuDetector,
+}
+// Calls on one session are serialised inside the library.
+unsafe impl Send for DigestSession<'_> {}
+unsafe impl Sync for DigestSession<'_> {}
+
+impl GpuDetector {
+    /// `omr_digest_begin` for a board of `rp.all_payloads_count` messages: `index_seed` as in
+    /// `encode_pertinent_indices`, `weight_seed` as in `encode_pertinent_payloads`; the work runs on
+    /// HIP's null stream.
+    pub fn digest_session(&self, rp: &RetrievalParams, index_seed: u64,
+                          weight_seed: &[u8; 32]) -> Result<DigestSession<'_>, OmrError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe {
+            omr_digest_begin(self.ctx, rp.all_payloads_count, rp.pertinent_count, index_seed, weight_seed.as_ptr(),
+                             std::ptr::null_mut(), &mut raw)
+        })?;
+        Ok(DigestSession { raw, _detector: self })
+    }
+}
+
+impl DigestSession<'_> {
+    /// Folds the messages `global_offset..global_offset + clues.len()` in (`omr_digest_update`);
+    /// returns when the device has finished with them.
+    pub fn update(&self, clues: &[Clue], payloads: &[Payload], global_offset: usize) -> Result<(), OmrError> {
+        if payloads.len() != clues.len() {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "one payload per message".into() });
+        }
+        let d = clues.len();
+        let mut a = Vec::with_capacity(d * OMR_N0);
+        let mut b = Vec::with_capacity(d * OMR_CLUE_COUNT);
+        for c in clues {
+            a.extend_from_slice(&c.a);
+            b.extend_from_slice(&c.b);
+        }
+        let pay: Vec<u16> = payloads.iter().flat_map(|p| p.iter().copied()).collect();
+        check(unsafe { omr_digest_update(self.raw, a.as_ptr(), b.as_ptr(), pay.as_ptr(), d, global_offset) })
+    }
+
+    /// The same on device buffers of the detector's GPU (`omr_digest_update_device`): returns once
+    /// enqueued.
+    ///
+    /// # Safety
+    /// The pointers must be device memory of `d` messages in the ABI layouts and stay valid until
+    /// `read` or `GpuDetector::check` has returned.
+    pub unsafe fn update_device(&self, d_clue_a: *const u16, d_clue_b: *const u16, d_payloads: *const u16, d: usize,
+                                global_offset: usize) -> Result<(), OmrError> {
+        check(omr_digest_update_device(self.raw, d_clue_a, d_clue_b, d_payloads, d, global_offset))
+    }
+
+    /// Adds another session's digest (e.g. another GPU's shard of the board) mod q2.
+    pub fn merge(&self, other: &Digest) -> Result<(), OmrError> {
+        let info = self.info()?;
+        if other.indices.len() != info.index_ct as usize || other.payloads.len() != info.payload_ct as usize {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "digest of another layout".into() });
+        }
+        let (idx, pay) = (NttRlwe::flatten(&other.indices), NttRlwe::flatten(&other.payloads));
+        check(unsafe { omr_digest_merge(self.raw, idx.as_ptr(), pay.as_ptr()) })
+    }
+
+    /// Waits for the session's work and returns the digest so far (`omr_digest_read`).
+    pub fn read(&self) -> Result<Digest, OmrError> {
+        let info = self.info()?;
+        let mut idx = vec![0u64; info.index_ct as usize * 2 * OMR_N2];
+        let mut pay = vec![0u64; info.payload_ct as usize * 2 * OMR_N2];
+        check(unsafe { omr_digest_read(self.raw, idx.as_mut_ptr(), pay.as_mut_ptr()) })?;
+        Ok(Digest { indices: idx.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect(),
+                    payloads: pay.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect() })
+    }
+
+    pub fn info(&self) -> Result<OmrDigestInfo, OmrError> {
+        let mut info = OmrDigestInfo::default();
+        check(unsafe { omr_digest_get_info(self.raw, &mut info) })?;
+        Ok(info)
+    }
+}
+
+impl Drop for DigestSession<'_> {
+    fn drop(&mut self) {
+        unsafe { omr_digest_destroy(self.raw) }
     }
 }
 

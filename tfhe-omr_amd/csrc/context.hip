@@ -10,7 +10,8 @@
 //
 // Top to bottom: the context (omr_ctx owns every device allocation through DevBuf, hip_util.hpp),
 // the launch helpers, context creation (tables from host_tables.hpp, keys, bounds and guards) and
-// the C ABI.
+// the C ABI. The digest session (digest.hip) runs the detect and encode bodies through
+// ctx_internal.hpp.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -25,6 +26,7 @@
 #include "br1_ntt.hpp"
 #include "br2_fft.hpp"
 #include "br2_ntt.hpp"
+#include "ctx_internal.hpp"
 #include "encode_kernels.hpp"
 #include "hip_util.hpp"
 #include "host_tables.hpp"
@@ -1053,30 +1055,53 @@ int encode_per_wg(size_t D, size_t max_chunks) {
   return (int)std::max(base, (D + max_chunks - 1) / max_chunks);
 }
 // The shared tail of the encode entry points: after the encode kernel's launch, reduce the chunk
-// partials into the n_ct output ciphertexts, then release the scratch.
-omr_status encode_finish(omr_ctx *c, int chunks, uint32_t n_ct, uint64_t *out, hipStream_t st) {
+// partials into the n_ct output ciphertexts (or add them to a running digest), then release the
+// scratch.
+omr_status encode_finish(omr_ctx *c, int chunks, uint32_t n_ct, uint64_t *out, hipStream_t st, bool accumulate) {
   HIP_TRY(hipGetLastError());
-  const size_t tot = (size_t)n_ct * 2 * N2;
-  reduce_partials_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(c->partial, chunks, (int)n_ct, out);
-  HIP_TRY(hipGetLastError());
+  omr_status s;
+  if (accumulate) {
+    if ((s = accumulate_partials(c->partial, chunks, n_ct, out, st)) != OMR_OK) return s;
+  } else {
+    const size_t tot = (size_t)n_ct * 2 * N2;
+    reduce_partials_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(c->partial, chunks, (int)n_ct, out);
+    HIP_TRY(hipGetLastError());
+  }
   return scratch_release(c, st);
 }
 }  // namespace
 
-extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, size_t D,
-                                                size_t offset, size_t all, uint64_t seed,
-                                                uint32_t first_ct, uint32_t n_ct, uint64_t *out,
-                                                void *stream) {
-  if (!c || !out || (D && !pv) || n_ct == 0 || offset + D > all || D > (size_t)INT32_MAX)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_indices_device: bad argument");
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;  // NULL: HIP's null stream
+// What digest.hip borrows (ctx_internal.hpp).
+namespace omr {
+
+std::mutex &ctx_mutex(omr_ctx *c) { return c->mu; }
+int ctx_device(const omr_ctx *c) { return c->device; }
+size_t ctx_batch(const omr_ctx *c) { return c->batch; }
+
+omr_status detect_device_locked(omr_ctx *c, const uint16_t *ca, const uint16_t *cb, size_t D, uint64_t *out,
+                                hipStream_t st) {
+  c->host_timing_valid = false;
+  return detect_device(c, ca, cb, D, out, st);
+}
+
+omr_status take_handoff_error_locked(omr_ctx *c) { return take_handoff_error(c); }
+
+omr_status accumulate_partials(const uint64_t *partial, int chunks, uint32_t n_ct, uint64_t *digest,
+                               hipStream_t st) {
+  const size_t tot = (size_t)n_ct * 2 * N2;
+  accumulate_partials_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(partial, chunks, (int)n_ct, digest);
+  HIP_TRY(hipGetLastError());
+  return OMR_OK;
+}
+
+omr_status encode_indices_locked(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all,
+                                 uint64_t seed, uint32_t first_ct, uint32_t n_ct, uint64_t *out, hipStream_t st,
+                                 bool accumulate) {
   omr_retrieval_params rp;
   omr_status s;
   if ((s = omr_get_retrieval_params(all, 0, &rp)) != OMR_OK) return s;
   if (D == 0) {
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
     return OMR_OK;
   }
   const int per_wg = encode_per_wg(D, c->enc_max_chunks);
@@ -1087,7 +1112,39 @@ extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, 
                   (int)rp.slots_per_segment, (int)rp.segment_per_cipher};
   encode_indices_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, (int)D, offset, ly, seed, first_ct,
                                                               per_wg, c->tb.tw2, c->partial);
-  return encode_finish(c, chunks, n_ct, out, st);
+  return encode_finish(c, chunks, n_ct, out, st, accumulate);
+}
+
+omr_status encode_payloads_locked(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                  size_t offset, size_t all, const uint16_t *weights, uint32_t n_ct,
+                                  uint32_t per_ct, uint64_t *out, hipStream_t st, bool accumulate) {
+  if (D == 0) {
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
+    return OMR_OK;
+  }
+  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
+  const int chunks = (int)((D + per_wg - 1) / per_wg);
+  omr_status s;
+  if ((s = ensure_partial(c, (size_t)n_ct * chunks * 2 * N2)) != OMR_OK) return s;
+  if ((s = scratch_acquire(c, st)) != OMR_OK) return s;
+  encode_payloads_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all,
+                                                               weights, (int)per_ct, per_wg,
+                                                               c->tb.tw2, c->partial);
+  return encode_finish(c, chunks, n_ct, out, st, accumulate);
+}
+
+}  // namespace omr
+
+extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, size_t D,
+                                                size_t offset, size_t all, uint64_t seed,
+                                                uint32_t first_ct, uint32_t n_ct, uint64_t *out,
+                                                void *stream) {
+  if (!c || !out || (D && !pv) || n_ct == 0 || offset + D > all || D > (size_t)INT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_indices_device: bad argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // NULL: HIP's null stream
+  return encode_indices_locked(c, pv, D, offset, all, seed, first_ct, n_ct, out, (hipStream_t)stream, false);
 }
 
 extern "C" omr_status omr_encode_payloads_device(omr_ctx *c, const uint64_t *pv,
@@ -1099,20 +1156,9 @@ extern "C" omr_status omr_encode_payloads_device(omr_ctx *c, const uint64_t *pv,
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_device: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;  // NULL: HIP's null stream
-  if (D == 0) {
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
-    return OMR_OK;
-  }
-  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
-  const int chunks = (int)((D + per_wg - 1) / per_wg);
-  omr_status s;
-  if ((s = ensure_partial(c, (size_t)n_ct * chunks * 2 * N2)) != OMR_OK) return s;
-  if ((s = scratch_acquire(c, st)) != OMR_OK) return s;
-  encode_payloads_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all,
-                                                               weights, (int)per_ct, per_wg,
-                                                               c->tb.tw2, c->partial);
-  return encode_finish(c, chunks, n_ct, out, st);
+  // NULL: HIP's null stream
+  return encode_payloads_locked(c, pv, payloads, D, offset, all, weights, n_ct, per_ct, out, (hipStream_t)stream,
+                                false);
 }
 
 extern "C" omr_status omr_encode_indices(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset,

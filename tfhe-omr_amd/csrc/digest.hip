@@ -1,0 +1,225 @@
+// Digest session (include/omr_gpu.h, omr_digest_*): the reference's board flow, detect every message,
+// encode_pertinent_indices per index ciphertext, encode_pertinent_payloads (examples/omr.rs:160-203,
+// detector.rs:223-453), run piece by piece inside the library. Per piece of at most the context's
+// detect batch: detect into the session's pertinency buffer, both encode kernels over it, and the
+// chunk partials added to the running digest mod q2. The digest is an exact sum mod q2 of
+// per-message terms, so any partition of the board into updates gives the same bits.
+//
+// The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
+// context's detect / encode scratch under the context mutex (ctx_internal.hpp), like any other call.
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "ctx_internal.hpp"
+#include "digest_ranges.hpp"
+
+using namespace omr;
+
+struct omr_digest {
+  omr_ctx *ctx;
+  hipStream_t st;  // NULL: HIP's null stream
+  size_t all;
+  uint64_t index_seed;
+  omr_retrieval_params rp;
+  DevBuf<uint16_t> weights;      // [payload_ct * cmb_count_per_cipher][all]
+  DevBuf<uint64_t> digest;       // [index_ct + payload_ct][2][N2], canonical
+  DevBuf<uint64_t> pv;           // pertinency ciphertexts of one piece, grown lazily
+  DevBuf<uint64_t> merge_stage;  // omr_digest_merge's upload
+  DevBuf<uint16_t> s_clue_a, s_clue_b, s_payloads;  // host updates' staging, grown together
+  DigestRanges ranges;
+  bool poisoned = false;  // a device-side failure may have reached the digest
+  std::mutex mu;
+
+  omr_digest(omr_ctx *c, hipStream_t s, size_t n, uint64_t seed) : ctx(c), st(s), all(n), index_seed(seed), ranges(n) {}
+  uint32_t n_idx() const { return rp.max_encode_indices_cipher_count; }
+  uint32_t n_pay() const { return rp.cmb_cipher_count; }
+  size_t digest_elems() const { return (size_t)(n_idx() + n_pay()) * 2 * N2; }
+};
+
+namespace {
+
+omr_status poisoned_error(const char *who) {
+  return set_error(OMR_ERR_DEVICE, std::string(who) + ": an earlier device failure invalidated this session's digest");
+}
+
+// Room for pieces of B messages; a buffer is reallocated only once the stream is done with it.
+omr_status ensure_piece(omr_digest *dg, size_t B, bool host) {
+  const bool grow_pv = !dg->pv.fits(B * 2 * N2);
+  const bool grow_stage = host && !(dg->s_clue_a.fits(B * N0) && dg->s_clue_b.fits(B * CLUES) &&
+                                    dg->s_payloads.fits(B * PAYLOAD_LEN));
+  if (!grow_pv && !grow_stage) return OMR_OK;
+  HIP_TRY(hipStreamSynchronize(dg->st));
+  if (grow_pv) HIP_TRY(dg->pv.reserve(B * 2 * N2));
+  if (grow_stage) {
+    HIP_TRY(dg->s_clue_a.reserve(B * N0));
+    HIP_TRY(dg->s_clue_b.reserve(B * CLUES));
+    HIP_TRY(dg->s_payloads.reserve(B * PAYLOAD_LEN));
+  }
+  return OMR_OK;
+}
+
+// One piece on the session's stream, the context mutex held: (stage,) detect, encode, accumulate.
+omr_status run_piece(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, const uint16_t *pay, size_t n,
+                     size_t offset, bool host) {
+  omr_ctx *c = dg->ctx;
+  hipStream_t st = dg->st;
+  if (host) {
+    HIP_TRY(hipMemcpyAsync(dg->s_clue_a, ca, n * N0 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dg->s_clue_b, cb, n * CLUES * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dg->s_payloads, pay, n * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    ca = dg->s_clue_a, cb = dg->s_clue_b, pay = dg->s_payloads;
+  }
+  omr_status s;
+  if ((s = detect_device_locked(c, ca, cb, n, dg->pv, st)) != OMR_OK) return s;
+  if ((s = encode_indices_locked(c, dg->pv, n, offset, dg->all, dg->index_seed, 0, dg->n_idx(), dg->digest, st,
+                                 true)) != OMR_OK)
+    return s;
+  return encode_payloads_locked(c, dg->pv, pay, n, offset, dg->all, dg->weights, dg->n_pay(),
+                                dg->rp.cmb_count_per_cipher, dg->digest + (size_t)dg->n_idx() * 2 * N2, st, true);
+}
+
+omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, const uint16_t *pay, size_t D,
+                         size_t offset, bool host, const char *who) {
+  if (!dg) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL session");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error(who);
+  if (D && (!ca || !cb || !pay)) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  if (!dg->ranges.can_insert(offset, D))
+    return set_error(OMR_ERR_INVALID_ARGUMENT,
+                     std::string(who) + ": the range reaches beyond the board or overlaps one already folded in");
+  if (D == 0) return OMR_OK;
+  omr_ctx *c = dg->ctx;
+  std::lock_guard<std::mutex> cl(ctx_mutex(c));
+  HIP_TRY(hipSetDevice(ctx_device(c)));
+  const size_t B = std::min(D, ctx_batch(c));
+  omr_status s;
+  if ((s = ensure_piece(dg, B, host)) != OMR_OK) return s;  // nothing enqueued yet: the session stays usable
+  try {
+    dg->ranges.insert(offset, D);
+  } catch (const std::bad_alloc &) {
+    return set_error(OMR_ERR_OUT_OF_MEMORY, std::string(who) + ": range bookkeeping");
+  }
+  for (size_t o = 0; o < D; o += B) {
+    const size_t n = std::min(B, D - o);
+    if ((s = run_piece(dg, ca + o * N0, cb + o * CLUES, pay + o * PAYLOAD_LEN, n, offset + o, host)) != OMR_OK) {
+      dg->poisoned = true;  // part of the range may already be in the digest
+      return s;
+    }
+  }
+  if (!host) return OMR_OK;
+  // as omr_detect_batch: the stream has finished with the host buffers, a failed hand-off is reported
+  if (hipStreamSynchronize(dg->st) != hipSuccess) {
+    dg->poisoned = true;
+    return set_error(OMR_ERR_DEVICE, std::string(who) + ": stream synchronisation failed");
+  }
+  if ((s = take_handoff_error_locked(c)) != OMR_OK) dg->poisoned = true;
+  return s;
+}
+
+}  // namespace
+
+extern "C" omr_status omr_digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
+                                       const uint8_t weight_seed[32], void *stream, omr_digest **out) {
+  if (!c || !weight_seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_begin: NULL argument");
+  *out = nullptr;
+  omr_retrieval_params rp;
+  omr_status s;
+  if ((s = omr_get_retrieval_params(all, pertinent, &rp)) != OMR_OK) return s;
+  HIP_TRY(hipSetDevice(ctx_device(c)));
+  try {
+    std::unique_ptr<omr_digest> dg(new omr_digest(c, (hipStream_t)stream, all, index_seed));
+    dg->rp = rp;
+    std::vector<uint16_t> w((size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * all);
+    if ((s = omr_payload_weights(weight_seed, all, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
+                                 w.data())) != OMR_OK)
+      return s;
+    HIP_TRY(dg->weights.upload_sync(w));
+    HIP_TRY(dg->digest.alloc(dg->digest_elems()));
+    HIP_TRY(hipMemsetAsync(dg->digest, 0, dg->digest_elems() * sizeof(uint64_t), dg->st));
+    HIP_TRY(hipStreamSynchronize(dg->st));
+    *out = dg.release();
+  } catch (const std::bad_alloc &) {
+    return set_error(OMR_ERR_OUT_OF_MEMORY, "omr_digest_begin: host allocation failed");
+  }
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
+                                        const uint16_t *payloads, size_t D, size_t offset) {
+  return digest_update(dg, ca, cb, payloads, D, offset, true, "omr_digest_update");
+}
+
+extern "C" omr_status omr_digest_update_device(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
+                                               const uint16_t *payloads, size_t D, size_t offset) {
+  return digest_update(dg, ca, cb, payloads, D, offset, false, "omr_digest_update_device");
+}
+
+extern "C" omr_status omr_digest_merge(omr_digest *dg, const uint64_t *idx_cts, const uint64_t *pay_cts) {
+  if (!dg || (!idx_cts && !pay_cts)) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge: NULL argument");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_merge");
+  const size_t ni = (size_t)dg->n_idx() * 2 * N2, np = (size_t)dg->n_pay() * 2 * N2;
+  for (size_t i = 0; idx_cts && i < ni; ++i)
+    if (idx_cts[i] >= Q2) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge: index digest value >= q2");
+  for (size_t i = 0; pay_cts && i < np; ++i)
+    if (pay_cts[i] >= Q2) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge: payload digest value >= q2");
+  HIP_TRY(hipSetDevice(ctx_device(dg->ctx)));
+  if (!dg->merge_stage.fits(ni + np)) {
+    HIP_TRY(hipStreamSynchronize(dg->st));
+    HIP_TRY(dg->merge_stage.reserve(ni + np));
+  }
+  // both uploads first: a failure there leaves the digest as it was
+  if (idx_cts)
+    HIP_TRY(hipMemcpyAsync(dg->merge_stage, idx_cts, ni * sizeof(uint64_t), hipMemcpyHostToDevice, dg->st));
+  if (pay_cts)
+    HIP_TRY(hipMemcpyAsync(dg->merge_stage + ni, pay_cts, np * sizeof(uint64_t), hipMemcpyHostToDevice, dg->st));
+  omr_status s = OMR_OK;
+  if (idx_cts) s = accumulate_partials(dg->merge_stage, 1, dg->n_idx(), dg->digest, dg->st);
+  if (s == OMR_OK && pay_cts) s = accumulate_partials(dg->merge_stage + ni, 1, dg->n_pay(), dg->digest + ni, dg->st);
+  if (s == OMR_OK && hipStreamSynchronize(dg->st) != hipSuccess)  // the host arrays may be reused
+    s = set_error(OMR_ERR_DEVICE, "omr_digest_merge: stream synchronisation failed");
+  if (s != OMR_OK) dg->poisoned = true;
+  return s;
+}
+
+extern "C" omr_status omr_digest_read(omr_digest *dg, uint64_t *idx_cts, uint64_t *pay_cts) {
+  if (!dg) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read: NULL session");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_read");
+  std::lock_guard<std::mutex> cl(ctx_mutex(dg->ctx));
+  HIP_TRY(hipSetDevice(ctx_device(dg->ctx)));
+  HIP_TRY(hipStreamSynchronize(dg->st));
+  omr_status s;
+  if ((s = take_handoff_error_locked(dg->ctx)) != OMR_OK) {
+    dg->poisoned = true;
+    return s;
+  }
+  const size_t ni = (size_t)dg->n_idx() * 2 * N2, np = (size_t)dg->n_pay() * 2 * N2;
+  if (idx_cts) HIP_TRY(hipMemcpy(idx_cts, dg->digest, ni * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (pay_cts) HIP_TRY(hipMemcpy(pay_cts, dg->digest + ni, np * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info) {
+  if (!dg || !info) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_get_info: NULL argument");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_get_info");
+  info->index_ct = dg->n_idx();
+  info->payload_ct = dg->n_pay();
+  info->combination_count = dg->rp.combination_count;
+  info->cmb_count_per_cipher = dg->rp.cmb_count_per_cipher;
+  info->all_payloads_count = dg->all;
+  info->messages = dg->ranges.covered();
+  info->pv_capacity_messages = dg->pv.capacity() / (2 * (size_t)N2);
+  return OMR_OK;
+}
+
+extern "C" void omr_digest_destroy(omr_digest *dg) {
+  if (!dg) return;
+  (void)hipSetDevice(ctx_device(dg->ctx));
+  (void)hipStreamSynchronize(dg->st);
+  delete dg;
+}

@@ -153,4 +153,19 @@ __global__ void reduce_partials_kernel(const uint64_t *__restrict__ partial, int
   out[idx] = s;
 }
 
+// digest[c][t] = (digest[c][t] + sum_chunk partial[c][chunk][t]) mod q2 (the digest session's
+// running sum, and omr_digest_merge with chunks = 1): canonical in, canonical out, as above.
+__global__ void accumulate_partials_kernel(const uint64_t *__restrict__ partial, int chunks,
+                                           int n_ct, uint64_t *__restrict__ digest) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)n_ct * 2 * N2) return;
+  const size_t c = idx / (2 * N2), t = idx % (2 * N2);
+  uint64_t s = digest[idx];
+  for (int k = 0; k < chunks; ++k) {
+    s += partial[((size_t)c * chunks + k) * 2 * N2 + t];
+    s = s >= Q2 ? s - Q2 : s;
+  }
+  digest[idx] = s;
+}
+
 }  // namespace omr

@@ -4,8 +4,10 @@
 // encode_pertinent_payloads, client-side retrieval, and a check that exactly the pertinent
 // indices and their payloads come back.
 //
-//   omr_e2e [-p payload_count] [-d device] [-s seed] [--host-only]
+//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--host-only]
 //
+// --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
+// PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -45,14 +47,17 @@ int main(int argc, char **argv) {
   int device = 0;
   uint64_t seed = 2025;
   bool host_only = false;
+  size_t session_piece = 0;  // --session: messages per omr_digest_update call
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if ((a == "-p" || a == "--payload-count") && i + 1 < argc) D = std::max<size_t>(1, std::stoull(argv[++i]));
     else if ((a == "-d" || a == "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
     else if ((a == "-s" || a == "--seed") && i + 1 < argc) seed = std::stoull(argv[++i]);
+    else if (a == "--session" && i + 1 < argc) session_piece = std::max<size_t>(1, std::stoull(argv[++i]));
     else if (a == "--host-only") host_only = true;
     else {
-      std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--host-only]\n", argv[0]);
+      std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--host-only]\n",
+                   argv[0]);
       return 2;
     }
   }
@@ -115,23 +120,46 @@ int main(int argc, char **argv) {
   omr_ctx *ctx = nullptr;
   omr_detection_key_view view{bsk1.data(), ksk.data(), bsk2.data(), tk.data()};
   CHECK(omr_ctx_create(&view, device, &ctx));
-  std::vector<uint64_t> pv(D * 2 * N2);
-  t = clk::now();
-  CHECK(omr_detect_batch(ctx, ca.data(), cb.data(), D, pv.data()));
-  const double td = secs(t);
-  std::printf("detect time: %.3f s (%.3f ms per message, host buffers)\n", td, td * 1e3 / D);
-
-  // encode_pertinent_indices x max_encode_indices_cipher_count, encode_pertinent_payloads
-  t = clk::now();
   const uint32_t n_idx = rp.max_encode_indices_cipher_count, n_pay = rp.cmb_cipher_count;
   std::vector<uint64_t> idx_ct((size_t)n_idx * 2 * N2), pay_ct((size_t)n_pay * 2 * N2);
-  for (uint32_t c = 0; c < n_idx; ++c)
-    CHECK(omr_encode_indices(ctx, pv.data(), D, 0, D, seed + 3, c, &idx_ct[(size_t)c * 2 * N2]));
-  std::printf("encode indices time: %.3f s\n", secs(t));
-  t = clk::now();
-  CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
-                            rp.cmb_count_per_cipher, pay_ct.data()));
-  std::printf("encode pertinent payloads time: %.3f s\n", secs(t));
+  if (session_piece) {
+    // the same flow inside the library, piece by piece (omr_digest_*): detect + both encoders
+    t = clk::now();
+    omr_digest *dg = nullptr;
+    CHECK(omr_digest_begin(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
+    for (size_t off = 0; off < D; off += session_piece) {
+      const size_t n = std::min(session_piece, D - off);
+      CHECK(omr_digest_update(dg, &ca[off * N0], &cb[off * CLUES], &payloads[off * PAYLOAD], n, off));
+    }
+    CHECK(omr_digest_read(dg, idx_ct.data(), pay_ct.data()));
+    omr_digest_info info;
+    CHECK(omr_digest_get_info(dg, &info));
+    omr_digest_destroy(dg);
+    const double ts = secs(t);
+    std::printf("digest session time: %.3f s (%.3f ms per message, host pieces of %zu, %zu messages folded in, "
+                "room for %zu pertinency ciphertexts)\n",
+                ts, ts * 1e3 / D, session_piece, info.messages, info.pv_capacity_messages);
+    if (info.messages != D) {
+      std::printf("FAILED\n");
+      return 1;
+    }
+  } else {
+    std::vector<uint64_t> pv(D * 2 * N2);
+    t = clk::now();
+    CHECK(omr_detect_batch(ctx, ca.data(), cb.data(), D, pv.data()));
+    const double td = secs(t);
+    std::printf("detect time: %.3f s (%.3f ms per message, host buffers)\n", td, td * 1e3 / D);
+
+    // encode_pertinent_indices x max_encode_indices_cipher_count, encode_pertinent_payloads
+    t = clk::now();
+    for (uint32_t c = 0; c < n_idx; ++c)
+      CHECK(omr_encode_indices(ctx, pv.data(), D, 0, D, seed + 3, c, &idx_ct[(size_t)c * 2 * N2]));
+    std::printf("encode indices time: %.3f s\n", secs(t));
+    t = clk::now();
+    CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
+                              rp.cmb_count_per_cipher, pay_ct.data()));
+    std::printf("encode pertinent payloads time: %.3f s\n", secs(t));
+  }
 
   // Retriever::decode_digest (omr.rs:216-218)
   t = clk::now();

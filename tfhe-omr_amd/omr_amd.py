@@ -54,6 +54,13 @@ class _Timing(C.Structure):
                 ("trace_separate", C.c_int)]
 
 
+class _DigestInfo(C.Structure):
+    """omr_digest_info."""
+    _fields_ = [("index_ct", C.c_uint32), ("payload_ct", C.c_uint32), ("combination_count", C.c_uint32),
+                ("cmb_count_per_cipher", C.c_uint32), ("all_payloads_count", C.c_size_t), ("messages", C.c_size_t),
+                ("pv_capacity_messages", C.c_size_t)]
+
+
 EXPORTS = {
     "omr_last_error": (C.c_char_p, []),
     "omr_version": (C.c_char_p, []),
@@ -99,6 +106,14 @@ EXPORTS = {
     "omr_encode_payloads_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                              C.c_void_p]),
+    "omr_digest_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_void_p)]),
+    "omr_digest_update": (C.c_int, [C.c_void_p, _u16p, _u16p, _u16p, C.c_size_t, C.c_size_t]),
+    "omr_digest_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "omr_digest_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_digest_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_digest_get_info": (C.c_int, [C.c_void_p, C.POINTER(_DigestInfo)]),
+    "omr_digest_destroy": (None, [C.c_void_p]),
     "omr_first_level": (C.c_int, [C.c_void_p, _u16p, _u16p, C.c_size_t, _u32p]),
     "omr_blind_rotate_level1": (C.c_int, [C.c_void_p, _u16p, _u16p, C.c_size_t, _u64p]),
     "omr_fft1_mul": (C.c_int, [C.c_void_p, _u32p, _u32p, C.c_size_t, _u64p]),
@@ -421,6 +436,8 @@ class Detector:
 
     def close(self):
         if getattr(self, "_h", None):
+            for dg in list(getattr(self, "_sessions", ())):  # a session must go before its context
+                dg.close()
             (_destroy_ctx or lib().omr_ctx_destroy)(self._h)
             self._h = None
 
@@ -570,6 +587,12 @@ class Detector:
                                                 d_weights, n_ct, per_ct, d_out, stream or None),
                "omr_encode_payloads_device")
 
+    def digest_session(self, all_payloads_count: int, pertinent_count: int, index_seed: int, weight_seed: bytes,
+                       stream: int = 0) -> "DigestSession":
+        """A digest session on this detector (omr_digest_begin): detect + encode a board piece by
+        piece without holding its pertinency vector. A context manager."""
+        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream)
+
     # ---- stage entry points (benches/two_level_bs.rs) ----
     def first_level(self, clue_a, clue_b) -> np.ndarray:
         clue_a = np.ascontiguousarray(clue_a, dtype=np.uint16).reshape(-1, N0)
@@ -608,6 +631,82 @@ class Detector:
         _check(lib().omr_blind_rotate_level2(self._h, lwe.reshape(-1), lwe.shape[0], out.reshape(-1)),
                "omr_blind_rotate_level2")
         return out
+
+
+class DigestSession:
+    """omr_digest_*: the board flow of examples/omr.rs:160-203 (detect, encode_pertinent_indices,
+    encode_pertinent_payloads) over message ranges fed in any order; the running digest stays on the
+    device and at most one detect chunk of pertinency ciphertexts is ever allocated."""
+
+    def __init__(self, detector: "Detector", all_payloads_count: int, pertinent_count: int, index_seed: int,
+                 weight_seed: bytes, stream: int = 0):
+        seed = np.frombuffer(bytes(weight_seed), dtype=np.uint8).copy()
+        if seed.size != 32:
+            raise OmrError("weight_seed must be 32 bytes")
+        h = C.c_void_p()
+        _check(lib().omr_digest_begin(detector.handle, all_payloads_count, pertinent_count, index_seed,
+                                      seed.ctypes.data, stream or None, C.byref(h)), "omr_digest_begin")
+        self._h = h
+        self._destroy = lib().omr_digest_destroy
+        self._detector = detector  # the context outlives the session
+        if not hasattr(detector, "_sessions"):
+            detector._sessions = weakref.WeakSet()
+        detector._sessions.add(self)
+        self._info = self.info()
+
+    def update(self, clue_a, clue_b, payloads, global_offset: int = 0) -> None:
+        """Host arrays u16 [D][512], [D][7], [D][612] for global indices global_offset..+D; returns
+        when the device has finished with them."""
+        a = np.ascontiguousarray(clue_a, dtype=np.uint16)
+        b = np.ascontiguousarray(clue_b, dtype=np.uint16)
+        p = np.ascontiguousarray(payloads, dtype=np.uint16)
+        D = a.shape[0]
+        if a.shape != (D, N0) or b.shape != (D, CLUE_COUNT) or p.shape != (D, PAYLOAD_LENGTH):
+            raise OmrError("clues must be u16 [D][512] and [D][7], payloads u16 [D][612]")
+        _check(lib().omr_digest_update(self._h, a.reshape(-1), b.reshape(-1), p.reshape(-1), D, global_offset),
+               "omr_digest_update")
+
+    def update_device(self, d_clue_a: int, d_clue_b: int, d_payloads: int, D: int, global_offset: int = 0) -> None:
+        """Device pointers (same layouts); enqueued on the session's stream, the caller keeps the
+        buffers alive until read() or Detector.check()."""
+        _check(lib().omr_digest_update_device(self._h, d_clue_a, d_clue_b, d_payloads, D, global_offset),
+               "omr_digest_update_device")
+
+    def merge(self, idx_cts, pay_cts) -> None:
+        """Add another session's read() output (e.g. another GPU's shard) mod q2."""
+        i = None if idx_cts is None else np.ascontiguousarray(idx_cts, dtype=np.uint64)
+        p = None if pay_cts is None else np.ascontiguousarray(pay_cts, dtype=np.uint64)
+        if (i is not None and i.size != self._info["index_ct"] * 2 * N2) or \
+                (p is not None and p.size != self._info["payload_ct"] * 2 * N2):
+            raise OmrError("digest arrays must be u64 [index_ct][2][2048] and [payload_ct][2][2048]")
+        _check(lib().omr_digest_merge(self._h, None if i is None else i.ctypes.data,
+                                      None if p is None else p.ctypes.data), "omr_digest_merge")
+
+    def read(self):
+        """(idx_cts u64 [index_ct][2][2048], pay_cts u64 [payload_ct][2][2048]) after a stream sync."""
+        idx = np.empty((self._info["index_ct"], 2, N2), np.uint64)
+        pay = np.empty((self._info["payload_ct"], 2, N2), np.uint64)
+        _check(lib().omr_digest_read(self._h, idx.ctypes.data, pay.ctypes.data), "omr_digest_read")
+        return idx, pay
+
+    def info(self) -> dict:
+        t = _DigestInfo()
+        _check(lib().omr_digest_get_info(self._h, C.byref(t)), "omr_digest_get_info")
+        return {n: getattr(t, n) for n, _ in _DigestInfo._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 def ntt(level: int, polys, inverse: bool = False, device: int = 0) -> np.ndarray:

@@ -215,3 +215,16 @@ class GpuBackend:
         self.det.encode_payloads_device(pv.data_ptr(), d_pay.data_ptr(), D, first, total, d_w.data_ptr(), n_pay,
                                         per, dig[n_idx:].data_ptr(), s)
         return dig
+
+    def digest(self, clue_a, clue_b, payloads, first, total, pertinent_count, index_seed, weight_seed):
+        """Detect + encode this rank's shard through a digest session (omr_digest_*) on the backend's
+        stream: device tensors clue_a int16 [D][512], clue_b int16 [D][7], payloads int16 [D][612]
+        with global indices first..first+D of a `total` board -> Digest of the shard (numpy u64,
+        canonical; shards of one board sum mod q2, e.g. with DigestSession.merge). The pertinency
+        vector is never held: at most one detect chunk of it exists inside the session."""
+        D = clue_a.shape[0]
+        with self.det.digest_session(total, pertinent_count, index_seed, weight_seed,
+                                     self.stream.cuda_stream) as dg:
+            dg.update_device(clue_a.data_ptr(), clue_b.data_ptr(), payloads.data_ptr(), D, first)
+            idx, pay = dg.read()  # synchronises the stream: the inputs are free again
+        return Digest(indices=idx, payloads=pay)
