@@ -261,11 +261,10 @@ omr_status omr_detect_batch_device(omr_ctx *ctx, const uint16_t *d_clue_a,
  *   second_level_ms total_second_level_bootstrapping_time  level-2 blind rotation
  *   trace_ms        total_trace_time                       hom_trace + NTT
  *   key_switch_ms   the sum + key-switch + mod-switch part of first_level_ms (two_level_bs.rs:62-73)
- * Timing modes (omr_ctx_enable_timing): 0 off; 1 stage events around the production kernels —
- * the throughput path fuses the trace into the level-2 kernel, so there trace_ms is 0,
- * second_level_ms includes it and trace_separate is 0; 2 the reference's split: the throughput
- * path runs the level-2 rotation and the trace as two launches (same output, slightly slower),
- * trace_separate = 1. The latency kernels always run the trace as its own launch. */
+ * Timing modes (omr_ctx_enable_timing): 0 off; 1 and 2 are the same, stage events around the
+ * production kernels. Both kernel families run the trace as its own launch after the level-2
+ * rotation, so trace_ms is always the reference's split. trace_separate is always 1; the field
+ * and the two mode numbers are kept for ABI compatibility. */
 typedef struct {
   float total_ms, first_level_ms, second_level_ms, trace_ms, key_switch_ms;
   size_t messages;
@@ -273,7 +272,7 @@ typedef struct {
 } omr_detect_timing;
 omr_status omr_ctx_enable_timing(omr_ctx *ctx, int mode);
 omr_status omr_last_timing(omr_ctx *ctx, omr_detect_timing *t);
-/* omr_detect_batch in timing mode 2 and omr_last_timing as one call under the context's lock
+/* omr_detect_batch with timing on and omr_last_timing as one call under the context's lock
  * (concurrent callers cannot switch timing off under each other or read another call's times);
  * the context's timing mode is left as it was. */
 omr_status omr_detect_with_time_info(omr_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,

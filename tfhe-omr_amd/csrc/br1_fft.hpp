@@ -160,10 +160,6 @@ __device__ __forceinline__ void br1f_digits(const uint32_t (&ac)[2][16], uint32_
 // barriers").
 constexpr int KROW_SLOTS = 2 * Fft512::N;  // double2 per staged row
 
-// Storage position of transform point (lane, e) within a BSK1 key polynomial: register-major, so
-// that each LDS-DMA instruction of krow_issue copies 1 KB contiguous (lane-major, 16 B per lane at
-// a 128 B stride: level 1 1 % slower, profiles/r03q/key_layout_ab.log).
-__device__ __forceinline__ int key1_pos(int lane, int e) { return e * 64 + lane; }
 constexpr int KROW_INSTR = 16 / BR1F_WPG;  // glds per wave per row
 
 // The key is read through a buffer descriptor (wave-uniform, SGPRs): each DMA instruction is

@@ -35,16 +35,6 @@ namespace omr {
 // as in br1f_kernel, and the rounded FFT product is exact in either order (device_fft.hpp).
 constexpr int BR1L_WAVES = 2 * D1;
 
-// BSK1 rows [512][8 r][2 o][lane * 8 + e] -> the latency layout [512][8 e][8 r][2 o][64 lane]
-__global__ __launch_bounds__(256) void bsk1_latency_layout_kernel(const double2 *__restrict__ in,
-                                                                  double2 *__restrict__ out, size_t n) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n) return;
-  const int lane = (int)(idx & 63), o = (int)((idx >> 6) & 1), r = (int)((idx >> 7) & 7), e = (int)((idx >> 10) & 7);
-  const size_t i = idx >> 13;
-  out[idx] = in[((i * 8 + r) * 2 + o) * 512 + key1_pos(lane, e)];
-}
-
 template <bool G>
 __device__ __forceinline__ void br1l_body(
     const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,

@@ -1,7 +1,7 @@
 // Level-1 blind rotation on the exact modular NTT (round 5): BlindRotationKey::blind_rotate with
 // concrete-ntt's arithmetic, as the reference runs it (detector.rs:553-557; omr_core/Cargo.toml:38-45).
 // Two uses:
-//  - the exact fallback of a guarded level-1 launch (context.hip, launch_br1): run after the guarded
+//  - the exact fallback of a guarded level-1 launch (detect.hip, launch_br1): run after the guarded
 //    FFT kernel, every workgroup reads that launch's rounding-margin word and leaves unless it
 //    reached the certificate threshold 1 - E1, in which case the launch's rotations are recomputed
 //    here and overwrite the FFT outputs -- so a key whose a priori bound does not prove the FFT exact
@@ -10,7 +10,7 @@
 //    FFT kernels (both families share the level-1 FFT) against an independent exact arithmetic.
 // One 64-thread workgroup (one wave) per rotation: WgNtt<Mod<1>, 64, 16> is wave-private (its
 // exchanges need no workgroup barrier), residues are exact integers in FP64 registers
-// (device_ntt.hpp), the key rows are read from L2 in the NTT domain x N1^-1 (context.hip, bsk1n:
+// (device_ntt.hpp), the key rows are read from L2 in the NTT domain x N1^-1 (context.hip, ensure_bsk1n:
 // [512][2 D1 rows][2 outputs][1024] centred doubles, NTT index order). Per CMUX step: the digits of
 // (X^a - 1) * ACC for both polynomials (the same decomposition as br1f: Lvl1Int::digits), 8 forward
 // transforms each multiplied into the two output accumulators, 2 inverse transforms, ACC += out.

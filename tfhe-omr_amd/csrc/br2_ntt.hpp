@@ -161,7 +161,7 @@ __global__ __launch_bounds__(BR2L_T, 1) void br2l_kernel(const uint32_t *__restr
                                                          uint64_t *__restrict__ out) {
   br2l_body(lwe_int, bsk2, tb, out);
 }
-// The exact fallback of a guarded throughput level-2 launch (context.hip, launch_br2): the same
+// The exact fallback of a guarded throughput level-2 launch (detect.hip, launch_br2): the same
 // rotation on the modular NTT, run only when that launch's observed rounding margin reached the
 // certificate threshold 1 - E2 (every workgroup reads the word and leaves otherwise).
 __global__ __launch_bounds__(BR2L_T, 1) void br2l_fallback_kernel(const uint32_t *__restrict__ lwe_int,

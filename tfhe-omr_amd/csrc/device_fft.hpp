@@ -426,4 +426,9 @@ struct WgFft {
 
 using Fft512 = WgFft<64, 8, 9>;  // level 1: N1 = 1024, one wave
 
+// Storage position of transform point (lane, e) within a BSK1 key polynomial: register-major, so
+// that each LDS-DMA instruction of krow_issue (br1_fft.hpp) copies 1 KB contiguous (lane-major, 16 B per lane at
+// a 128 B stride: level 1 1 % slower, profiles/r03q/key_layout_ab.log).
+__device__ __forceinline__ int key1_pos(int lane, int e) { return e * 64 + lane; }
+
 }  // namespace omr

@@ -6,14 +6,14 @@
 // per-message terms, so any partition of the board into updates gives the same bits.
 //
 // The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
-// context's detect / encode scratch under the context mutex (ctx_internal.hpp), like any other call.
+// context's detect / encode scratch under the context mutex (ctx.hpp), like any other call.
 #include <algorithm>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
-#include "ctx_internal.hpp"
+#include "ctx.hpp"
 #include "digest_ranges.hpp"
 
 using namespace omr;
@@ -72,13 +72,10 @@ omr_status run_piece(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, con
     HIP_TRY(hipMemcpyAsync(dg->s_payloads, pay, n * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     ca = dg->s_clue_a, cb = dg->s_clue_b, pay = dg->s_payloads;
   }
-  omr_status s;
-  if ((s = detect_device_locked(c, ca, cb, n, dg->pv, st)) != OMR_OK) return s;
-  if ((s = encode_indices_locked(c, dg->pv, n, offset, dg->all, dg->index_seed, 0, dg->n_idx(), dg->digest, st,
-                                 true)) != OMR_OK)
-    return s;
-  return encode_payloads_locked(c, dg->pv, pay, n, offset, dg->all, dg->weights, dg->n_pay(),
-                                dg->rp.cmb_count_per_cipher, dg->digest + (size_t)dg->n_idx() * 2 * N2, st, true);
+  OMR_TRY(detect_device(c, ca, cb, n, dg->pv, st));
+  OMR_TRY(encode_indices(c, dg->pv, n, offset, dg->all, dg->index_seed, 0, dg->n_idx(), dg->digest, st, true));
+  return encode_payloads(c, dg->pv, pay, n, offset, dg->all, dg->weights, dg->n_pay(), dg->rp.cmb_count_per_cipher,
+                         dg->digest + (size_t)dg->n_idx() * 2 * N2, st, true);
 }
 
 omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, const uint16_t *pay, size_t D,
@@ -92,11 +89,11 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
                      std::string(who) + ": the range reaches beyond the board or overlaps one already folded in");
   if (D == 0) return OMR_OK;
   omr_ctx *c = dg->ctx;
-  std::lock_guard<std::mutex> cl(ctx_mutex(c));
-  HIP_TRY(hipSetDevice(ctx_device(c)));
-  const size_t B = std::min(D, ctx_batch(c));
+  std::lock_guard<std::mutex> cl(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t B = std::min(D, c->batch);
   omr_status s;
-  if ((s = ensure_piece(dg, B, host)) != OMR_OK) return s;  // nothing enqueued yet: the session stays usable
+  OMR_TRY(ensure_piece(dg, B, host));  // nothing enqueued yet: the session stays usable
   try {
     dg->ranges.insert(offset, D);
   } catch (const std::bad_alloc &) {
@@ -115,7 +112,7 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
     dg->poisoned = true;
     return set_error(OMR_ERR_DEVICE, std::string(who) + ": stream synchronisation failed");
   }
-  if ((s = take_handoff_error_locked(c)) != OMR_OK) dg->poisoned = true;
+  if ((s = take_handoff_error(c)) != OMR_OK) dg->poisoned = true;
   return s;
 }
 
@@ -127,8 +124,8 @@ extern "C" omr_status omr_digest_begin(omr_ctx *c, size_t all, size_t pertinent,
   *out = nullptr;
   omr_retrieval_params rp;
   omr_status s;
-  if ((s = omr_get_retrieval_params(all, pertinent, &rp)) != OMR_OK) return s;
-  HIP_TRY(hipSetDevice(ctx_device(c)));
+  OMR_TRY(omr_get_retrieval_params(all, pertinent, &rp));
+  HIP_TRY(hipSetDevice(c->device));
   try {
     std::unique_ptr<omr_digest> dg(new omr_digest(c, (hipStream_t)stream, all, index_seed));
     dg->rp = rp;
@@ -166,7 +163,7 @@ extern "C" omr_status omr_digest_merge(omr_digest *dg, const uint64_t *idx_cts, 
     if (idx_cts[i] >= Q2) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge: index digest value >= q2");
   for (size_t i = 0; pay_cts && i < np; ++i)
     if (pay_cts[i] >= Q2) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge: payload digest value >= q2");
-  HIP_TRY(hipSetDevice(ctx_device(dg->ctx)));
+  HIP_TRY(hipSetDevice(dg->ctx->device));
   if (!dg->merge_stage.fits(ni + np)) {
     HIP_TRY(hipStreamSynchronize(dg->st));
     HIP_TRY(dg->merge_stage.reserve(ni + np));
@@ -189,11 +186,11 @@ extern "C" omr_status omr_digest_read(omr_digest *dg, uint64_t *idx_cts, uint64_
   if (!dg) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read: NULL session");
   std::lock_guard<std::mutex> lk(dg->mu);
   if (dg->poisoned) return poisoned_error("omr_digest_read");
-  std::lock_guard<std::mutex> cl(ctx_mutex(dg->ctx));
-  HIP_TRY(hipSetDevice(ctx_device(dg->ctx)));
+  std::lock_guard<std::mutex> cl(dg->ctx->mu);
+  HIP_TRY(hipSetDevice(dg->ctx->device));
   HIP_TRY(hipStreamSynchronize(dg->st));
   omr_status s;
-  if ((s = take_handoff_error_locked(dg->ctx)) != OMR_OK) {
+  if ((s = take_handoff_error(dg->ctx)) != OMR_OK) {
     dg->poisoned = true;
     return s;
   }
@@ -219,7 +216,7 @@ extern "C" omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info)
 
 extern "C" void omr_digest_destroy(omr_digest *dg) {
   if (!dg) return;
-  (void)hipSetDevice(ctx_device(dg->ctx));
+  (void)hipSetDevice(dg->ctx->device);
   (void)hipStreamSynchronize(dg->st);
   delete dg;
 }

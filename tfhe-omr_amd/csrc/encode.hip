@@ -1,0 +1,138 @@
+// Encode (detector.rs:223-453): the index and payload encode kernels' launches over the context's
+// partial-sum scratch, their reduction or accumulation, and the four encode entry points.
+#include <algorithm>
+
+#include "ctx.hpp"
+#include "encode_kernels.hpp"
+
+using namespace omr;
+
+namespace {
+// Messages per encode workgroup: at least 32 (128 from D = 16,384), and at most max_chunks
+// (default 4,096) chunk partials per ciphertext (scratch n_ct x chunks x 32 KiB: 3.7 GB for 28
+// ciphertexts at D = 2^20); above ENC_T messages the index kernel stages its buckets in blocks.
+int encode_per_wg(size_t D, size_t max_chunks) {
+  const size_t base = D >= 16384 ? 128 : 32;
+  return (int)std::max(base, (D + max_chunks - 1) / max_chunks);
+}
+// The shared tail of the encode bodies: after the encode kernel's launch, reduce the chunk partials
+// into the n_ct output ciphertexts (or add them to a running digest).
+omr_status encode_finish(omr_ctx *c, int chunks, uint32_t n_ct, uint64_t *out, hipStream_t st, bool accumulate) {
+  HIP_TRY(hipGetLastError());
+  if (accumulate) return accumulate_partials(c->scr.partial, chunks, n_ct, out, st);
+  const size_t tot = (size_t)n_ct * 2 * N2;
+  reduce_partials_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(c->scr.partial, chunks, (int)n_ct, out);
+  HIP_TRY(hipGetLastError());
+  return OMR_OK;
+}
+}  // namespace
+
+omr_status omr::accumulate_partials(const uint64_t *partial, int chunks, uint32_t n_ct, uint64_t *digest,
+                                    hipStream_t st) {
+  const size_t tot = (size_t)n_ct * 2 * N2;
+  accumulate_partials_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(partial, chunks, (int)n_ct, digest);
+  HIP_TRY(hipGetLastError());
+  return OMR_OK;
+}
+
+omr_status omr::encode_indices(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all, uint64_t seed,
+                               uint32_t first_ct, uint32_t n_ct, uint64_t *out, hipStream_t st, bool accumulate) {
+  omr_retrieval_params rp;
+  OMR_TRY(omr_get_retrieval_params(all, 0, &rp));
+  if (D == 0) {
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
+    return OMR_OK;
+  }
+  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
+  const int chunks = (int)((D + per_wg - 1) / per_wg);
+  OMR_TRY(ensure_partial(c, (size_t)n_ct * chunks * 2 * N2));
+  ScratchLease lease;
+  OMR_TRY(lease.acquire(c, st));
+  EncodeLayout ly{(int)rp.index_slots_per_bucket, (int)rp.slots_per_bucket,
+                  (int)rp.slots_per_segment, (int)rp.segment_per_cipher};
+  encode_indices_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, (int)D, offset, ly, seed, first_ct,
+                                                              per_wg, c->tab.tb.tw2, c->scr.partial);
+  OMR_TRY(encode_finish(c, chunks, n_ct, out, st, accumulate));
+  return lease.release();
+}
+
+omr_status omr::encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, size_t offset,
+                                size_t all, const uint16_t *weights, uint32_t n_ct, uint32_t per_ct, uint64_t *out,
+                                hipStream_t st, bool accumulate) {
+  if (D == 0) {
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
+    return OMR_OK;
+  }
+  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
+  const int chunks = (int)((D + per_wg - 1) / per_wg);
+  OMR_TRY(ensure_partial(c, (size_t)n_ct * chunks * 2 * N2));
+  ScratchLease lease;
+  OMR_TRY(lease.acquire(c, st));
+  encode_payloads_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all,
+                                                               weights, (int)per_ct, per_wg,
+                                                               c->tab.tb.tw2, c->scr.partial);
+  OMR_TRY(encode_finish(c, chunks, n_ct, out, st, accumulate));
+  return lease.release();
+}
+
+extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, size_t D,
+                                                size_t offset, size_t all, uint64_t seed,
+                                                uint32_t first_ct, uint32_t n_ct, uint64_t *out,
+                                                void *stream) {
+  if (!c || !out || (D && !pv) || n_ct == 0 || offset + D > all || D > (size_t)INT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_indices_device: bad argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // NULL: HIP's null stream
+  return encode_indices(c, pv, D, offset, all, seed, first_ct, n_ct, out, (hipStream_t)stream, false);
+}
+
+extern "C" omr_status omr_encode_payloads_device(omr_ctx *c, const uint64_t *pv,
+                                                 const uint16_t *payloads, size_t D, size_t offset,
+                                                 size_t all, const uint16_t *weights, uint32_t n_ct,
+                                                 uint32_t per_ct, uint64_t *out, void *stream) {
+  if (!c || !out || (D && (!pv || !payloads || !weights)) || n_ct == 0 || per_ct == 0 ||
+      per_ct * PAYLOAD_LEN > (uint32_t)N2 || offset + D > all || D > (size_t)INT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_device: bad argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // NULL: HIP's null stream
+  return encode_payloads(c, pv, payloads, D, offset, all, weights, n_ct, per_ct, out, (hipStream_t)stream, false);
+}
+
+extern "C" omr_status omr_encode_indices(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset,
+                                         size_t all, uint64_t seed, uint32_t ct, uint64_t *out) {
+  if (!c || !out || (D && !pv)) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_indices");
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<uint64_t> dpv, dout;
+  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
+  HIP_TRY(dout.alloc(2 * N2));
+  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  OMR_TRY(omr_encode_indices_device(c, dpv, D, offset, all, seed, ct, 1, dout, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(out, dout, 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
+                                          size_t D, size_t offset, size_t all,
+                                          const uint16_t *weights, uint32_t n_ct, uint32_t per_ct,
+                                          uint64_t *out) {
+  if (!c || !out || (D && (!pv || !payloads || !weights)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t wn = (size_t)n_ct * per_ct * all;
+  DevBuf<uint64_t> dpv, dout;
+  DevBuf<uint16_t> dpay, dw;
+  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
+  HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
+  HIP_TRY(dw.alloc(std::max<size_t>(wn, 1)));
+  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
+  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dw, weights, wn * sizeof(uint16_t), hipMemcpyHostToDevice));
+  OMR_TRY(omr_encode_payloads_device(c, dpv, dpay, D, offset, all, dw, n_ct, per_ct, dout, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}

@@ -8,7 +8,7 @@
 //    radix-2 tree FFT in double-double arithmetic with double-double twiddles (accuracy ~2^-100)
 //    and rounded once to FP64, so every stored spectral value K^ obeys |K^ - K| <= u |K| (u = 2^-53)
 //    instead of carrying an FP64 transform error (key_spectrum_dd_kernel);
-//  - kappa_r, the largest |K^| of every stored key row (row_max_abs_kernel): the only key-dependent
+//  - kappa_r, the largest |K^| of every stored key row (row_max_abs_kernel, key_convert.hpp): the only key-dependent
 //    constants of the a priori bound on |computed - exact| of every rounded product coefficient,
 //    E = n D max over steps and outputs of [(2 delta_f + u') sum_r kappa_r + sqrt(2) u sum_k w_k
 //    kappa_r(k)] (host_tables.hpp: apriori_bound);
@@ -105,28 +105,11 @@ __device__ __forceinline__ void wave_max_publish(double v, unsigned long long *w
   for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
   if ((threadIdx.x & 63) == 0) atomicMax(word, (unsigned long long)__double_as_longlong(v));
 }
-// Largest |K^| of each stored key-spectrum row (len complex values; one workgroup per row):
-// kappa_r of the a priori bound, rounded up past sqrt's error.
-__global__ __launch_bounds__(256) void row_max_abs_kernel(const double2 *__restrict__ x, int len,
-                                                          double *__restrict__ out) {
-  __shared__ double wm[4];
-  const double2 *row = x + (size_t)blockIdx.x * len;
-  double m = 0.0;
-  for (int i = threadIdx.x; i < len; i += 256) {
-    const double2 v = row[i];
-    m = fmax(m, sqrt(v.x * v.x + v.y * v.y) * (1.0 + 0x1p-50));
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) m = fmax(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
-}
 
 // ---- rounding-margin guard ----------------------------------------------------------------------
 // RoundGuard<true>::note(y, r) keeps max |y - r| (r = the integer y was rounded to); publish()
 // leaves it in *word (one atomic per wave). RoundGuard<false> compiles to nothing: the production
-// kernels are the G = false instantiations, the guarded ones separate kernels (context.hip).
+// kernels are the G = false instantiations, the guarded ones separate kernels (launched by detect.hip).
 template <bool G>
 struct RoundGuard {
   double m = 0.0;
@@ -138,20 +121,14 @@ struct RoundGuard {
   }
 };
 
-// ---- the exactness contract of a context (context.hip) -----------------------------------------
+// ---- the exactness contract of a context (ctx.hpp: omr_ctx::Exactness) ------------------------
 // Guard words per context: [0, 1] the largest margin of levels 1, 2 since the last reset (what
 // omr_ctx_rounding_margin reports), [2, 3] the margin of the launch in flight (zeroed before each
 // guarded launch, written by its kernels), [4, 5] the number of launches whose margin reached the
 // threshold 1 - E (that launch was then re-run on the exact NTT: br1n_fallback_kernel,
-// br2l_fallback_kernel + trace_fallback_kernel).
+// br2l_fallback_kernel + trace_fallback_kernel; detect.hip's guard_fold_kernel keeps [0, 1] and [4, 5]).
 constexpr int GUARD_WORDS = 6;
 constexpr int GUARD_ERR_HANDOFF = 1;  // bit of the context's error word: a two-CU hand-off timed out
-__global__ void guard_fold_kernel(unsigned long long *words, int level, double thr) {
-  if (threadIdx.x != 0) return;
-  const unsigned long long m = words[2 + level];
-  atomicMax(&words[level], m);
-  if (__longlong_as_double((long long)m) >= thr) atomicAdd(&words[4 + level], 1ull);
-}
 // What every workgroup of an exact fallback kernel asks first: did the guarded launch's observed
 // rounding margin reach the certificate threshold 1 - E? (It leaves at once otherwise.)
 __device__ __forceinline__ bool margin_breached(const unsigned long long *word, double thr) {

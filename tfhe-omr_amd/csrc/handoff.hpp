@@ -1,6 +1,6 @@
 // Hand-offs between the workgroups of a cooperative latency kernel (br2x_kernel, br2y_kernel,
 // trace_x_kernel) through global memory: the sc1 accesses, the flag protocol, and the geometry of
-// the payload slots and flags, which the kernels index and the host (context.hip) allocates from the
+// the payload slots and flags, which the kernels index and the host (detect.hip) allocates from the
 // same functions and constants. Also the phase timestamps of the latency kernels.
 //
 // Protocol (MI355X_MICROARCH.md, inter-workgroup visibility, the first row of the sc1 table): every

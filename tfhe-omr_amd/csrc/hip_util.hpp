@@ -15,6 +15,12 @@
     hipError_t _e = (expr);                                              \
     if (_e != hipSuccess) return omr::hip_error(#expr, _e);              \
   } while (0)
+// The same for a call of the library's own that returns omr_status (its error text is already set).
+#define OMR_TRY(expr)                \
+  do {                               \
+    omr_status _s = (expr);          \
+    if (_s != OMR_OK) return _s;     \
+  } while (0)
 
 namespace omr {
 

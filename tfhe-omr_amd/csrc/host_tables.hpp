@@ -9,8 +9,8 @@
 #include <cmath>
 #include <vector>
 
-#include "br2_fft.hpp"
 #include "exactness.hpp"
+#include "fft1024.hpp"
 #include "host_ring.hpp"
 
 namespace omr {
@@ -128,7 +128,7 @@ inline std::vector<double2> fft_twiddles() {
   return tw;
 }
 
-// Fft1024 twiddles (br2_fft.hpp): pass p = 1..4, block hi -> (B, A, AB) at tw_off(p) + 3 hi (the
+// Fft1024 twiddles (fft1024.hpp): pass p = 1..4, block hi -> (B, A, AB) at tw_off(p) + 3 hi (the
 // inverse), then the forward's tangent forms (cos, tan) of (A, B) at TW_LEN + ct_off(p) + 2 hi, with
 // A = W(2p, hi), B = W(2p + 1, 2 hi) of the tree with n = 1024 (eps(0, 0) = n, w = e^{i pi / 2n});
 // each entry an exact angle evaluated in long double and rounded once.

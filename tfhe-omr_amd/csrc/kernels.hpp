@@ -1,5 +1,6 @@
-// Kernels of the detect / encode path (gfx950). Each kernel cites the reference function it
-// replaces; the launch code is in context.hip.
+// Geometry, tables and the plain NTT kernel shared by the detect / encode path (gfx950). Each kernel of
+// the path cites the reference function it replaces; the launch code is in detect.hip and encode.hip,
+// the key conversion in key_convert.hpp (context.hip).
 #pragma once
 
 #include "device_ntt.hpp"
@@ -15,6 +16,11 @@ constexpr int BR2_T = 256, BR2_E = 8;  // N2 = 2048
 constexpr int ENC_T = 128, ENC_E = 16;
 constexpr size_t OMR_DEFAULT_BATCH = 16384;  // messages per detect chunk (scratch 36 KiB/msg)
 constexpr size_t OMR_ENC_MAX_CHUNKS = 4096;   // default chunk partials per encode ciphertext
+// key-switch geometry (ks_mfma.hpp; the KSK's conversion is in key_convert.hpp)
+constexpr int KSM_COLS = 672;  // NI + 1 = 671 output columns, padded to 21 tiles of 32
+constexpr int KSM_LIMBS = 4;
+constexpr size_t KSKB_WORDS = (size_t)N1 * KSM_LIMBS * KSM_COLS * 8;  // 32 int8 per (i, l, col)
+constexpr int KS_SPLIT = 32;  // slices of the 1024 input coefficients
 
 struct DeviceTables {
   const double *tw1, *itw1, *tw2, *itw2;  // psi^brv(k), psi^-brv(k) (centred)
@@ -39,28 +45,6 @@ __device__ __forceinline__ double rot_read(const double *p, int j, int r) {
     s = 1.0;
   }
   return s * p[t];
-}
-
-// ---- key conversion: coefficient-domain canonical residues -> NTT-domain centred residues ----
-template <int LEVEL, typename IN, typename OUT>
-__global__ void key_to_ntt_kernel(const IN *in, OUT *out, size_t npoly, double scale,
-                                  const double *tw) {
-  using M = Mod<LEVEL>;
-  constexpr int T = LEVEL == 1 ? BR1_T : BR2_T, E = LEVEL == 1 ? BR1_E : BR2_E;
-  using NTT = WgNtt<M, T, E>;
-  __shared__ double lds[NTT::LDS_DOUBLES];
-  const size_t poly = blockIdx.x;
-  const int tid = threadIdx.x;
-  if (poly >= npoly) return;
-  const IN *src = in + poly * M::N;
-  double x[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) x[e] = from_u64<M>((uint64_t)src[tid + e * T]);
-  NTT::fwd(x, lds, tw, tid);
-  OUT *dst = out + poly * M::N + tid * E;
-#pragma unroll
-  for (int e = 0; e < E; ++e)
-    dst[e] = (OUT)(scale == 1.0 ? canon<M>(x[e]) : canon<M>(mm<M>(canon<M>(x[e]), scale)));
 }
 
 // ---- plain NTT of canonical u64 polynomials (tests / omr_ntt) ----

@@ -4,8 +4,8 @@
 // transform rounded once to FP64, which the a priori error bound of DESIGN.md §3 relies on.
 #pragma once
 
-#include "br2_fft.hpp"
 #include "exactness.hpp"
+#include "fft1024.hpp"
 
 namespace omr {
 

@@ -8,39 +8,16 @@
 // v_mfma_i32_32x32x32_i8 per (32 messages x 32 columns x 32 digits x limb). Per limb the int32
 // sums stay below 27648 * 127 < 2^22; acc = sum_l C_l 2^(7 l) < 2^43 is exact in int64 and then
 // reduced mod q1 like the oracle's u64 sum, so the output is bit-identical.
+// The geometry (KSM_COLS, KSM_LIMBS, KSKB_WORDS, KS_SPLIT) is in kernels.hpp, the KSK's conversion to
+// the int8 limbs (ksk_to_i8_kernel) in key_convert.hpp.
 #pragma once
 
 #include "kernels.hpp"
 
 namespace omr {
 
-constexpr int KSM_COLS = 672;  // NI + 1 = 671 output columns, padded to 21 tiles of 32
-constexpr int KSM_LIMBS = 4;
-constexpr size_t KSKB_WORDS = (size_t)N1 * KSM_LIMBS * KSM_COLS * 8;  // 32 int8 per (i, l, col)
-
 typedef int omr_v4i __attribute__((ext_vector_type(4)));
 typedef int omr_v16i __attribute__((ext_vector_type(16)));
-
-// KSK u32 [1024][27][671] -> int8 limbs [1024][4][672][32] (packed 4 per u32 word, byte b of word
-// w = digit 4 w + b), zero for digits >= 27 and column 671.
-__global__ void ksk_to_i8_kernel(const uint32_t *__restrict__ ksk, uint32_t *__restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= KSKB_WORDS) return;
-  const int w = (int)(t & 7);
-  const size_t rest = t >> 3;
-  const int col = (int)(rest % KSM_COLS);
-  const size_t il = rest / KSM_COLS;
-  const int limb = (int)(il & 3), i = (int)(il >> 2);
-  uint32_t word = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int j = 4 * w + b;
-    uint32_t v = 0;
-    if (j < KS_DIGITS && col <= NI) v = (ksk[((size_t)i * KS_DIGITS + j) * (NI + 1) + col] >> (7 * limb)) & 127u;
-    word |= v << (8 * b);
-  }
-  out[t] = word;
-}
 
 // Output column `col` of one message from the exact key-switch sum (detector.rs:560-594):
 // b' = b - sum (columns < 670: -sum), modulus switch q1 -> 4096 (round half up), and the
@@ -120,7 +97,6 @@ __global__ void sum7_kernel(const uint32_t *__restrict__ ext, uint32_t *__restri
 
 // ---- key switch, split over the input coefficients (the latency path: a lone message otherwise
 // gets 21 waves for 88 MB of KSK) ------------------------------------------------------------------
-constexpr int KS_SPLIT = 32;  // slices of the 1024 input coefficients
 
 // grid (ceil(B / 64), 21, KS_SPLIT): ks_mfma_kernel's tile over input coefficients
 // [z * 1024 / KS_SPLIT, (z + 1) * 1024 / KS_SPLIT); int32 limb sums to part[z][m][col][limb].

@@ -528,8 +528,8 @@ class Detector:
         return out.view(np.complex128)
 
     def enable_timing(self, mode: int = 1):
-        """0 off; 1 stage events around the production kernels; 2 the reference's split (the
-        trace as its own launch: the throughput path's production form since round 5)."""
+        """0 off; 1 and 2 are the same, stage events around the production kernels (the trace is
+        always its own launch, so trace_separate is always 1)."""
         _check(lib().omr_ctx_enable_timing(self._h, int(mode)), "omr_ctx_enable_timing")
 
     def last_timing(self) -> dict:

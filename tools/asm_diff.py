@@ -1,4 +1,5 @@
-"""Compare two device listings (make asm: build/context.s) kernel by kernel.
+"""Compare two device listings (make asm: build/<unit>.s per translation unit with kernels; concatenate
+them, `cat build/context.s build/detect.s build/encode.s`) kernel by kernel.
 
     python tools/asm_diff.py OLD.s NEW.s
 

@@ -1,6 +1,6 @@
 """Per-step ISA census of a kernel's CMUX step loop from a hipcc -S listing.
 
-    python tools/isa_census.py <context.s> <kernel> <block>=<count> [<block>=<count> ...] [--json out]
+    python tools/isa_census.py <detect.s> <kernel> <block>=<count> [<block>=<count> ...] [--json out]
 
 Each <block> is a basic-block label of the kernel (e.g. .LBB2_17) and <count> how many times one CMUX
 step executes it (from the loop structure: tools/block_stats.py lists the blocks). The census sums

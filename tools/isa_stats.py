@@ -1,4 +1,4 @@
-"""Instruction statistics of one kernel in a hipcc -S listing (build/context.s):
+"""Instruction statistics of one kernel in a hipcc -S listing (make asm: build/detect.s):
 python tools/isa_stats.py <file.s> <kernel-substring> [more files...]"""
 import collections
 import sys
