@@ -1,4 +1,4 @@
-"""The closed-form gadget digits used by the kernels (br1_fft.hpp Lvl1Int::digits/digit,
+"""The closed-form gadget digits used by the kernels (level1_common.hpp Lvl1Int::digits/digit,
 level2_common.hpp Digits2) equal the recursive signed decomposition of the oracle
 (NonPowOf2ApproxSignedBasis: y = floor((v + 2^(drop-1)) / 2^drop), balanced digits, unbounded
 top digit) on boundary and random canonical residues."""

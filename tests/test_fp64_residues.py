@@ -1,5 +1,5 @@
 """The FP64 residue canonicalisation the kernels use (device_ntt.hpp canon / canon_small with
-OMR_CANON_RED, br1_fft.hpp Lvl1Int::canon with BR1F_CANON_MIN), replayed in numpy with the
+OMR_CANON_RED, level1_common.hpp Lvl1Int::canon with BR1F_CANON_MIN), replayed in numpy with the
 device's IEEE operations: red(x) = x - rint(x * fl(1/q)) * q (the product q * rint(...) and the
 difference are exact in FP64 here, as the device's fma is), rint = round half to even.
 
@@ -152,7 +152,7 @@ def test_inverse_twiddles_mirror_forward_table():
 
 
 def test_level1_magic_round_reduce():
-    """br1_fft.hpp Lvl1Int::round_red: for y = integer + e (|y| < 2^43, |e| < 0.01, an FFT product
+    """level1_common.hpp Lvl1Int::round_red: for y = integer + e (|y| < 2^43, |e| < 0.01, an FFT product
     output), r = y - rint(y / q) q keeps the fraction exactly, and the low 32 bits of r + 1.5 * 2^52
     are round(r) = round(y) mod q (centred, |.| <= (q + 1) / 2) in two's complement."""
     q = Q1

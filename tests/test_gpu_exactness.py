@@ -2,7 +2,7 @@
 
 The reference computes every external product with an exact modular NTT (concrete-ntt,
 omr_core/Cargo.toml:38-45; detector.rs:553-557, :623). The throughput kernels here use FP64
-FFTs and round (br1_fft.hpp, br2_fft.hpp; the latency level 1 too), so these tests prove the
+FFTs and round (br1_fft.hpp with level1_common.hpp, br2_fft.hpp; the latency level 1 too), so these tests prove the
 rounding exact on bench.py's own keys and clues (pack 42, key seed 7, clue seeds 1000 / 1001):
 
 - the rounding-margin guard (exactness.hpp) over one 65,536-message launch: the largest
@@ -305,6 +305,17 @@ def test_high_kappa_level1_key_rerun_exact():
         try:
             ref = orc.detect_batch(ca, cb)
             lwe = np.stack([orc.first_level(ca[i], cb[i]) for i in range(3)])
+            # the mode-1 rotation entry (five LWEs: 4 + 1 in br1f's workgroups): br1n_fallback_kernel
+            # overwrites the full RLWE output of either guarded family
+            rng = np.random.default_rng(81)
+            la = rng.integers(0, 2048, size=(5, 512), dtype=np.uint16)
+            lb = rng.integers(0, 2048, size=5, dtype=np.uint16)
+            ref_rot = np.stack([orc.br1(la[m], lb[m]) for m in range(5)])
+            for thr in (0, 64):
+                before = det.exactness()["breaches"][0]
+                det.set_latency_threshold(thr)
+                assert np.array_equal(det.blind_rotate_level1(la, lb), ref_rot), f"level-1 rotation entry, threshold {thr}"
+                assert det.exactness()["breaches"][0] > before, thr
         finally:
             orc.close()
         assert np.array_equal(got, ref), "guarded high-kappa level-1 detect differs from the oracle"

@@ -346,15 +346,35 @@ def test_gpu_keygen_matches_oracle_and_detects():
     assert np.array_equal(det.detect_batch(ca, cb), want)
 
 
-def test_level1_rotations_both_paths(real, path):
-    """omr_blind_rotate_level1 (full RLWE output) on explicit LWEs, incl. a = 0 steps and the
-    extreme phases, bit-exact against the oracle's blind rotation."""
-    _, det, orc = real
+def _level1_lwes():
+    """Five LWEs (4 + 1: three tail slots in a br1f workgroup) with a = 0 steps and the extreme phases."""
     rng = np.random.default_rng(17)
     la = rng.integers(0, 2048, (5, A.N0)).astype(np.uint16)
     la[1, ::3] = 0
     lb = np.array([0, 1, 1023, 1024, 2047], np.uint16)
+    return la, lb
+
+
+def test_level1_rotations_both_paths(real, path):
+    """omr_blind_rotate_level1 (full RLWE output) on explicit LWEs, incl. a = 0 steps and the
+    extreme phases, bit-exact against the oracle's blind rotation."""
+    _, det, orc = real
+    la, lb = _level1_lwes()
     got = det.blind_rotate_level1(la, lb)
+    for m in range(5):
+        assert np.array_equal(got[m], orc.br1(la[m], lb[m])), f"rotation {m}"
+
+
+def test_level1_rotations_guarded_both_paths(real, path):
+    """The same rotations on the guarded kernels (br1l_guard_kernel, br1f_guard_kernel) in mode 1:
+    the full RLWE output goes through the store the plain kernels share, bit-exact against the oracle."""
+    _, det, orc = real
+    la, lb = _level1_lwes()
+    det.set_rounding_guard(True)
+    try:
+        got = det.blind_rotate_level1(la, lb)
+    finally:
+        det.set_rounding_guard(False)
     for m in range(5):
         assert np.array_equal(got[m], orc.br1(la[m], lb[m])), f"rotation {m}"
 

@@ -1,4 +1,4 @@
-"""Integer models of br1f's accumulator representation (tfhe-omr_amd/csrc/br1_fft.hpp, Lvl1Off and
+"""Integer models of br1f's accumulator representation (tfhe-omr_amd/csrc/level1_common.hpp, Lvl1Off and
 Lvl1Int::round_mod), in numpy with explicit u32 wrap-around, against the plain definitions:
 
 - ac'' = ac + H/2 (mod Q) in [0, Q); the stored negacyclic half n = H - ac'' (signed u32);

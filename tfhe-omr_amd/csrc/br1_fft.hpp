@@ -13,138 +13,24 @@
 #pragma once
 
 #include "device_fft.hpp"
-#include "exactness.hpp"
-#include "kernels.hpp"
+#include "level1_common.hpp"
 
 namespace omr {
 
 constexpr int BR1F_WPG = 4;  // level-1 waves (rotations) per workgroup, kept in lockstep per CMUX step
 
-struct Lvl1Int {
-  static constexpr int Q = 134215681, H = 67107840;
-  __device__ static __forceinline__ int canon(int x) {  // |x| < q + H -> [-H, H]
-    // unsigned min folds, no VCC (compare/select pairs serialise on VCC with hazard NOPs):
-    // y = x + H in [-Q, 2Q); min(y, y + Q) lifts [-Q, 0) into [0, Q), min(y, y - Q) lowers
-    // [Q, 2Q) into [0, Q) (the other operand wraps above 2^31 and loses)
-    uint32_t y = (uint32_t)(x + H);
-    y = min(y, y + (uint32_t)Q);
-    y = min(y, y - (uint32_t)Q);
-    return (int)y - H;
-  }
-  __device__ static __forceinline__ uint32_t to_u32(int x) { return (uint32_t)(x < 0 ? x + Q : x); }
-  // y = an integer + e (|y| < 2^43, |e| < 0.1: an FFT product output): round(y) mod q in [0, q], as
-  // a u32. The quotient is floor(y / q) (as computed: it may exceed the true floor only when y is
-  // within 2^-37 q of a multiple of q, and then r rounds to 0; it may fall one short only when the
-  // rounded result is q), r = y - kq keeps the fraction, and adding 1.5 * 2^52 rounds r to the
-  // nearest integer in the low mantissa bits: one FP64 add instead of rint + conversion. The result
-  // q (= 0 mod q) is allowed: Lvl1Off::add folds it. With a RoundGuard, |r - round(r)| =
-  // |y - rint(y)| (r = y - kq is exact) is recorded.
-  template <bool G = false>
-  __device__ static __forceinline__ uint32_t round_mod(double y, RoundGuard<G> *rg = nullptr) {
-    const double r = __fma_rn(-floor(y * (1.0 / 134215681.0)), 134215681.0, y);
-    const double s = r + 6755399441055744.0;
-    if constexpr (G) rg->note(r, s - 6755399441055744.0);
-    return (uint32_t)__builtin_bit_cast(uint64_t, s);
-  }
-  // NonPowOf2ApproxSignedBasis (logB 5, d 4, drop 7) on a canonical residue: y = floor((v + 2^6)
-  // / 2^7) has balanced base-32 digits d_k in [-16, 15] (k < 3) and an unbounded top digit; in
-  // closed form, with y' = y + 16 (1 + 32 + 32^2): d_k = ((y' >> 5k) & 31) - 16 for k < 3 and
-  // d_3 = y' >> 15 (the same digits as the recursive Digits8<LOGB1, D1, DROP1>). The word kept is
-  // y' ^ (16 (1 + 32 + 32^2)): field k then holds d_k in two's complement (d_k + 16 = f in
-  // [0, 32) and (f - 16) mod 32 = f ^ 16), the top digit is unchanged, and every digit is one
-  // signed bit-field extract with wave-uniform offset and width (Lvl1Off::digit_u). Returns that word.
-  static constexpr int DIGIT_BIAS = ((1 << (LOGB1 * (D1 - 1))) - 1) / ((1 << LOGB1) - 1) * (1 << (LOGB1 - 1));
-  __device__ static __forceinline__ uint32_t digits(int v) {
-    return (uint32_t)(((v + (1 << (DROP1 - 1))) >> DROP1) + DIGIT_BIAS) ^ (uint32_t)DIGIT_BIAS;
-  }
-};
-
-// br1f keeps ACC offset by H/2: ac'' in [0, Q) with ac'' = ac + H/2 (mod Q). The stored negacyclic
-// extension n = H - ac'' = -ac + H/2 is then in the same representation (as a signed u32, in
-// [-H, H]) and is also the operand of the digit word: for a rotated entry x'' (either half),
-// t = x'' + n = (x - ac) + H (mod Q) with t in (-Q, 2Q), so one v_min3_u32(t, t + Q, t - Q) (the
-// wrapped operands lose) is canon(x - ac) + H in [0, Q), and the digit word of the canonical
-// residue y - H is ((y - H + 2^6 + 2^7 DIGIT_BIAS) >> 7) ^ DIGIT_BIAS (the bias folded in before
-// the shift; the shift itself folds into the extraction offsets, digits_u): 5 integer operations
-// per word. The accumulator update adds a
-// rounded product in [0, Q] (Lvl1Int::round_mod): s in [0, 2Q), min(s, s - Q), 3 operations.
-struct Lvl1Off {
-  static constexpr uint32_t Q = (uint32_t)Lvl1Int::Q, H = (uint32_t)Lvl1Int::H, OFF = H / 2;
-  static_assert(H % 2 == 0, "H/2 offset");
-  __device__ static __forceinline__ uint32_t fold(uint32_t y, uint32_t yq, uint32_t ymq) {  // y, y + Q, y - Q
-    return min(min(y, yq), ymq);
-  }
-  // centred value v in [-H, H] -> ac''
-  __device__ static __forceinline__ uint32_t enc(int v) {
-    const uint32_t y = (uint32_t)(v + (int)OFF);
-    return min(y, y + Q);
-  }
-  // ac'' -> centred value in [-H, H]
-  __device__ static __forceinline__ int dec(uint32_t acpp) { return Lvl1Int::canon((int)acpp - (int)OFF); }
-  // the stored negacyclic half "-ac + H/2" and the digit operand
-  __device__ static __forceinline__ uint32_t neg(uint32_t acpp) { return H - acpp; }
-  // digit word of canon(x - ac) from a stored entry x'' and n = neg(ac''): t = x - ac + H; the
-  // Lvl1Int::digits word before its shift by DROP1 (bits 7.. hold the fields, bits 0..6 the dropped
-  // remainder, never read): the shift folds into the extraction offsets (digit_u / digit_shifts_u),
-  // one operation fewer per word. Both br1l and br1f use it (br1f since round 5: at 248 VGPRs it no
-  // longer spills; same speed, profiles/r05n/bench_variants.log).
-  __device__ static __forceinline__ uint32_t digits_u(uint32_t xs, uint32_t n) {
-    const uint32_t t = xs + n;
-    const uint32_t y = fold(t, t + Q, t - Q);
-    constexpr uint32_t C = (uint32_t)((1 << (DROP1 - 1)) - Lvl1Int::H + (Lvl1Int::DIGIT_BIAS << DROP1));
-    return (y + C) ^ ((uint32_t)Lvl1Int::DIGIT_BIAS << DROP1);
-  }
-  // signed digit k of a digits_u() word: one v_bfe_i32 at offset DROP1 + 5 k (the top digit: the
-  // word's sign-extended rest)
-  __device__ static __forceinline__ double digit_u(uint32_t w, int k) {
-    return (double)(int)__builtin_amdgcn_sbfe(w, DROP1 + LOGB1 * k, k < D1 - 1 ? LOGB1 : 32 - DROP1 - LOGB1 * (D1 - 1));
-  }
-  // signed digit k of a digits_u() word by two shifts
-  __device__ static __forceinline__ double digit_shifts_u(uint32_t w, int k) {
-    const int s1 = k < D1 - 1 ? 32 - DROP1 - LOGB1 * (k + 1) : 0;
-    const int s2 = k < D1 - 1 ? 32 - LOGB1 : DROP1 + LOGB1 * (D1 - 1);
-    return (double)((int)(w << s1) >> s2);
-  }
-  // ac'' + r for r in [0, Q], reduced to [0, Q)
-  __device__ static __forceinline__ uint32_t add(uint32_t acpp, uint32_t r) {
-    const uint32_t s = acpp + r;
-    return min(s, s - Q);
-  }
-  template <bool G>
-  __device__ static __forceinline__ uint32_t round(double y, RoundGuard<G> *rg) { return Lvl1Int::round_mod<G>(y, rg); }
-};
-
-// ACC layout: ac[p][h * 8 + e] = coefficient lane + 64 e + 512 h of poly p (0 mask, 1 body).
-__device__ __forceinline__ int acc_coef(int lane, int i) { return lane + 64 * (i & 7) + 512 * (i >> 3); }
-
-// digits of (X^a - 1) * ACC for both polys. Each poly is staged with its negacyclic extension
-// ext = [ACC, -ACC] (2N int32 = the wave's 8 KB buffer st), so (X^a * ACC)[j] = ext[(j - a) mod 2N]:
-// no sign fix-up per coefficient. st is 8 KB-aligned (br1f_body), so the LDS byte address of
-// entry (j - a) mod 2N is st | ((4 (lane - a) + 256 i) & 8191) for coefficient j = lane + 64 i:
-// one add and one v_and_or_b32 per read.
-// (ACC in the Lvl1Off representation: ext = [ac'', H - ac''], every entry "value + H/2".)
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
+// digits of (X^a - 1) * ACC for both polys, each staged in turn as [ac'', H - ac''] in the wave's
+// 8 KB buffer st (8 KB-aligned: br1f_body) and read back rotated (level1_common.hpp).
 __device__ __forceinline__ void br1f_digits(const uint32_t (&ac)[2][16], uint32_t *st, int a, int lane,
                                             uint32_t (&pk)[2][16]) {
-  const uint32_t sbase = (uint32_t)(size_t)(lds_u32 *)st;
-  const uint32_t b4 = (uint32_t)(lane - a) * 4u;
-  const uint32_t kWrap = 8u * N1 - 1;  // 8 KB - 1 (no VOP3 literals on gfx9: an SGPR operand)
+  const Lvl1RotRead rot(st, lane, a);
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     uint32_t n[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      n[i] = Lvl1Off::neg(ac[p][i]);
-      st[acc_coef(lane, i)] = ac[p][i];
-      st[N1 + acc_coef(lane, i)] = n[i];
-    }
+    lvl1_stage_ext(st, ac[p], lane, n);
     wave_lds_sync();
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {  // acc_coef(0, i) = 64 i
-      uint32_t addr;  // ((b4 + 256 i) & 8191) | sbase in one v_and_or_b32 (not formed by the compiler)
-      asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(addr) : "v"(b4 + 256u * i), "s"(kWrap), "v"(sbase));  // one SGPR per VOP3 on gfx9
-      pk[p][i] = Lvl1Off::digits_u(*(const lds_u32 *)(size_t)addr, n[i]);
-    }
+    for (int i = 0; i < 16; ++i) pk[p][i] = Lvl1Off::digits_u(rot(i), n[i]);
     wave_lds_fence();  // the next poly's writes stay below these reads
   }
 }
@@ -183,10 +69,10 @@ __device__ __forceinline__ void krow_issue(__amdgpu_buffer_rsrc_t rsrc, int q,
   }
 }
 __device__ __forceinline__ void vm_wait_row_in_flight() {  // s_waitcnt vmcnt(KROW_INSTR)
-  __builtin_amdgcn_s_waitcnt((KROW_INSTR & 0xF) | ((KROW_INSTR >> 4) << 14) | (0x7 << 4) | (0xF << 8));
+  __builtin_amdgcn_s_waitcnt(waitcnt_vm(KROW_INSTR));
 }
 __device__ __forceinline__ void vm_wait_all() {  // s_waitcnt vmcnt(0)
-  __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));
+  __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));
 }
 
 // One GGSW row q = q0 + p D1 + k of a CMUX step: digit k of poly p, forward transform,
@@ -226,10 +112,7 @@ __device__ __forceinline__ void br1f_row(const uint32_t (&pk)[16], int k, int q,
       outr[1][e] = __fma_rn(xr[0][e], kB.x, -xi[0][e] * kB.y);
       outi[1][e] = __fma_rn(xr[0][e], kB.y, xi[0][e] * kB.x);
     } else {
-      outr[0][e] = __fma_rn(xr[0][e], ka.x, __fma_rn(-xi[0][e], ka.y, outr[0][e]));
-      outi[0][e] = __fma_rn(xr[0][e], ka.y, __fma_rn(xi[0][e], ka.x, outi[0][e]));
-      outr[1][e] = __fma_rn(xr[0][e], kB.x, __fma_rn(-xi[0][e], kB.y, outr[1][e]));
-      outi[1][e] = __fma_rn(xr[0][e], kB.y, __fma_rn(xi[0][e], kB.x, outi[1][e]));
+      lvl1_mac(xr[0][e], xi[0][e], ka, kB, outr[0][e], outi[0][e], outr[1][e], outi[1][e]);
     }
   }
 }
@@ -296,6 +179,10 @@ __device__ __forceinline__ void br1f_body(
   uint16_t *la = la_all[wave];
   const size_t g = item * W + wave;
   const size_t gi = g < nrot ? g : nrot - 1;  // a tail slot recomputes the last rotation
+  // The LWE staging and the initial accumulator are level1_common.hpp's lvl1_stage_lwe and
+  // lvl1_acc_init written out: through the helpers the prologue comes out 72 bytes shorter, which
+  // moves the (instruction-identical) CMUX loop to another fetch alignment and costs 0.7 % of the
+  // kernel's time (2,168 -> 2,183 ms per 65,536 messages). Keep the three in step.
   int b;
   if (lwe_a == nullptr) {  // extract clue c of message m (CmLweCiphertext::extract_all, :514)
     const size_t m = gi / CLUES;
@@ -308,9 +195,9 @@ __device__ __forceinline__ void br1f_body(
     for (int i = lane; i < N0; i += 64) la[i] = lwe_a[gi * N0 + i] & (Q0 - 1);
     b = lwe_b[gi] & (Q0 - 1);
   }
+  const int r0 = (2 * N1 - (b % (2 * N1))) % (2 * N1);
   // ACC = (0, X^{-b} * LUT1)
   uint32_t ac[2][16];  // Lvl1Off: ac + OFF
-  const int r0 = (2 * N1 - (b % (2 * N1))) % (2 * N1);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     ac[0][i] = Lvl1Off::enc(0);
@@ -351,26 +238,8 @@ __device__ __forceinline__ void br1f_body(
   rg.publish(margin);
   __syncthreads();
   if (g >= nrot) return;
-  if (mode == 0) {  // extract_lwe_locally (coefficient 0), detector.rs:561
-    int *st = reinterpret_cast<int *>(xch);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st[acc_coef(lane, i)] = Lvl1Off::dec(ac[0][i]);
-    wave_lds_sync();
-    uint32_t *o = ext + g * (N1 + 1);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int j = acc_coef(lane, i);
-      o[j] = Lvl1Int::to_u32(j == 0 ? st[0] : -st[N1 - j]);
-    }
-    if (lane == 0) o[N1] = Lvl1Int::to_u32(Lvl1Off::dec(ac[1][0]));
-  } else {
-    uint64_t *o = rlwe_out + g * 2 * N1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      o[acc_coef(lane, i)] = Lvl1Int::to_u32(Lvl1Off::dec(ac[0][i]));
-      o[N1 + acc_coef(lane, i)] = Lvl1Int::to_u32(Lvl1Off::dec(ac[1][i]));
-    }
-  }
+  lvl1_store_wave([&](int p, int i) { return Lvl1Off::dec(ac[p][i]); }, reinterpret_cast<int *>(xch), g, mode, ext,
+                  rlwe_out, lane);
 }
 
 __global__ __launch_bounds__(64 * BR1F_WPG, 2) void br1f_kernel(

@@ -16,8 +16,9 @@
 // points), so the outputs are bit-identical; tests/test_gpu_parity.py checks both paths.
 #pragma once
 
-#include "br1_fft.hpp"
+#include "device_fft.hpp"
 #include "handoff.hpp"
+#include "level1_common.hpp"
 
 namespace omr {
 
@@ -54,33 +55,14 @@ __device__ __forceinline__ void br1l_body(
   const int p = wave / D1, k = wave % D1;
   double2 *xch = xch_all[wave];
   const size_t g = blockIdx.x;  // rotation
-  int b;
-  if (lwe_a == nullptr) {  // clue g % 7 of message g / 7 (CmLweCiphertext::extract_all, :514)
-    const size_t m = g / CLUES;
-    const int c = (int)(g % CLUES);
-    const uint16_t *A = clue_a + m * N0;
-    for (int i = threadIdx.x; i < N0; i += 64 * W)
-      la[i] = i <= c ? (uint16_t)(A[c - i] & (Q0 - 1)) : (uint16_t)((Q0 - A[N0 + c - i]) & (Q0 - 1));
-    b = clue_b[m * CLUES + c] & (Q0 - 1);
-  } else {
-    for (int i = threadIdx.x; i < N0; i += 64 * W) la[i] = lwe_a[g * N0 + i] & (Q0 - 1);
-    b = lwe_b[g] & (Q0 - 1);
-  }
-  const int r0 = (2 * N1 - (b % (2 * N1))) % (2 * N1);
+  const int b = lvl1_stage_lwe(clue_a, clue_b, lwe_a, lwe_b, g, la, threadIdx.x, 64 * W);
   // ACC = (0, X^{-b} * LUT1): wave 0 owns the mask accumulator, wave 1 the body accumulator
   // (the accumulator in br1f's Lvl1Off form: ac'' = ac + H/2 in [0, Q), the stored negacyclic half
-  // H - ac'' doubling as the digit operand; br1_fft.hpp, tests/test_lvl1_offset_model.py)
+  // H - ac'' doubling as the digit operand; level1_common.hpp, tests/test_lvl1_offset_model.py)
   uint32_t ac[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
-    ac[i] = Lvl1Off::enc(wave == 1 ? (int)canon_small<Mod<1>>(rot_read<N1>(tb.lut1, acc_coef(lane, i), r0)) : 0);
-  if (wave < 2) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      ext[wave][acc_coef(lane, i)] = ac[i];
-      ext[wave][N1 + acc_coef(lane, i)] = Lvl1Off::neg(ac[i]);
-    }
-  }
+  for (int i = 0; i < 16; ++i) ac[i] = Lvl1Off::enc(wave == 1 ? (int)lvl1_acc_init(tb, b, acc_coef(lane, i)) : 0);
+  if (wave < 2) lvl1_stage_ext(ext[wave], ac, lane);
   for (int j = threadIdx.x; j < NF; j += 64 * W) tws[j] = tb.fft1[j];
   __syncthreads();
   // Wave v's key slice of an executed step: rows 0..7, outputs A / B at register slot v of every
@@ -101,22 +83,16 @@ __device__ __forceinline__ void br1l_body(
   const int pslot = __builtin_amdgcn_readfirstlane(blockIdx.x == 0 ? wave : -1);
   int hs = 0;
   RoundGuard<G> rg;  // waves 0 / 1 round the inverses
-  (void)pslot;
-  (void)hs;
   // one CMUX step at executed step i with its key slice kk (kko: the other slice buffer; inext,
   // inext2: the next two executed steps)
   auto cmux = [&](int i, double2 (&kk)[8][2], double2 (&kko)[8][2], int inext, int inext2) {
     const int a = __builtin_amdgcn_readfirstlane(la[i]);  // != 0: (X^0 - 1) * ACC = 0 is skipped
     OMR_PHASE(pslot, hs, 0);
     double xr[1][8], xi[1][8];
-    const uint32_t sbase = (uint32_t)(size_t)(lds_u32 *)ext[p], b4 = (uint32_t)(lane - a) * 4u;
-    const uint32_t kWrap = 8u * N1 - 1;  // as br1f_digits: ((b4 + 256 q) & 8191) | sbase
+    const Lvl1RotRead rot(ext[p], lane, a);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int j = acc_coef(lane, q);
-      uint32_t addr;
-      asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(addr) : "v"(b4 + 256u * q), "s"(kWrap), "v"(sbase));
-      const uint32_t w = Lvl1Off::digits_u(*(const lds_u32 *)(size_t)addr, ext[p][N1 + j]);
+      const uint32_t w = Lvl1Off::digits_u(rot(q), ext[p][N1 + acc_coef(lane, q)]);
       const double d = Lvl1Off::digit_shifts_u(w, k);
       if (q < 8)
         xr[0][q] = d;
@@ -140,11 +116,7 @@ __device__ __forceinline__ void br1l_body(
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         const double2 x = xch_all[r][wave * 64 + lane];
-        const double2 ka = kk[r][0], kB = kk[r][1];
-        ar = __fma_rn(x.x, ka.x, __fma_rn(-x.y, ka.y, ar));
-        ai = __fma_rn(x.x, ka.y, __fma_rn(x.y, ka.x, ai));
-        br = __fma_rn(x.x, kB.x, __fma_rn(-x.y, kB.y, br));
-        bi = __fma_rn(x.x, kB.y, __fma_rn(x.y, kB.x, bi));
+        lvl1_mac(x.x, x.y, kk[r][0], kk[r][1], ar, ai, br, bi);
       }
       outs[0][wave * 64 + lane] = make_double2(ar, ai);
       outs[1][wave * 64 + lane] = make_double2(br, bi);
@@ -167,11 +139,9 @@ __device__ __forceinline__ void br1l_body(
       F::inv<1, false>(sr, si, xch, tws, lane);
       OMR_PHASE(pslot, hs, 6);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
+      for (int q = 0; q < 16; ++q)
         ac[q] = Lvl1Off::add(ac[q], Lvl1Off::round<G>(q < 8 ? sr[0][q] : si[0][q - 8], &rg));  // exact (< 2^43)
-        ext[wave][acc_coef(lane, q)] = ac[q];
-        ext[wave][N1 + acc_coef(lane, q)] = Lvl1Off::neg(ac[q]);
-      }
+      lvl1_stage_ext(ext[wave], ac, lane);
     }
     wg_barrier_lds();  // ACC staged for the next step's digits
     OMR_PHASE(pslot, hs, 7);

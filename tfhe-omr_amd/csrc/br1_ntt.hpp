@@ -17,19 +17,14 @@
 // Not tuned: a fallback that never runs on a real key, and a test instrument.
 #pragma once
 
-#include "br1_fft.hpp"
+#include "kernels.hpp"
+#include "level1_common.hpp"
 
 namespace omr {
 
 using Ntt1W = WgNtt<Mod<1>, 64, 16>;
 static_assert(Ntt1W::N == N1 && Ntt1W::LDS_DOUBLES * sizeof(double) >= 2 * N1 * sizeof(int),
               "the exchange buffer also stages [ACC, -ACC]");
-
-// signed digit k of an Lvl1Int::digits word: fields of LOGB1 bits from bit 0, the top digit the
-// sign-extended rest
-__device__ __forceinline__ double lvl1_digit(uint32_t w, int k) {
-  return (double)(int)__builtin_amdgcn_sbfe(w, LOGB1 * k, k < D1 - 1 ? LOGB1 : 32 - LOGB1 * (D1 - 1));
-}
 
 // Rotation g: clue g % 7 of message g / 7 (lwe_a == nullptr) or LWE g; the outputs as br1f_body's
 // (mode 0: the extracted LWE, mode 1: the full RLWE).
@@ -42,25 +37,13 @@ __device__ __forceinline__ void br1n_body(const uint16_t *__restrict__ clue_a, c
   __shared__ double lds[Ntt1W::LDS_DOUBLES];  // the transforms' exchanges; [ACC, -ACC] between them
   __shared__ uint16_t la[N0];
   const int lane = threadIdx.x;
-  int b;
-  if (lwe_a == nullptr) {  // CmLweCiphertext::extract_all (:514), as br1f_body
-    const size_t m = g / CLUES;
-    const int c = (int)(g % CLUES);
-    const uint16_t *A = clue_a + m * N0;
-    for (int i = lane; i < N0; i += 64)
-      la[i] = i <= c ? (uint16_t)(A[c - i] & (Q0 - 1)) : (uint16_t)((Q0 - A[N0 + c - i]) & (Q0 - 1));
-    b = clue_b[m * CLUES + c] & (Q0 - 1);
-  } else {
-    for (int i = lane; i < N0; i += 64) la[i] = lwe_a[g * N0 + i] & (Q0 - 1);
-    b = lwe_b[g] & (Q0 - 1);
-  }
+  const int b = lvl1_stage_lwe(clue_a, clue_b, lwe_a, lwe_b, g, la, lane, 64);
   // ACC = (0, X^{-b} * LUT1); ac[p][e] = coefficient lane + 64 e, canonical centred
   double ac[2][16];
-  const int r0 = (2 * N1 - (b % (2 * N1))) % (2 * N1);
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     ac[0][e] = 0.0;
-    ac[1][e] = canon_small<M>(rot_read<N1>(tb.lut1, lane + 64 * e, r0));
+    ac[1][e] = lvl1_acc_init(tb, b, lane + 64 * e);
   }
   __syncthreads();
   int *st = reinterpret_cast<int *>(lds);
@@ -75,13 +58,13 @@ __device__ __forceinline__ void br1n_body(const uint16_t *__restrict__ clue_a, c
         st[lane + 64 * e] = (int)ac[p][e];
         st[N1 + lane + 64 * e] = -(int)ac[p][e];
       }
-      Ntt1W::wave_sync();
+      wave_lds_sync();
 #pragma unroll
       for (int e = 0; e < 16; ++e) {  // (X^a ACC)[j] = [ACC, -ACC][(j - a) mod 2N]
         const int x = st[(lane + 64 * e - a) & (2 * N1 - 1)];
         w[p][e] = Lvl1Int::digits(Lvl1Int::canon(x - (int)ac[p][e]));
       }
-      Ntt1W::wave_sync();  // the reads are done before the buffer is written again
+      wave_lds_sync();  // the reads are done before the buffer is written again
     }
     double o[2][16];
 #pragma unroll
@@ -110,25 +93,7 @@ __device__ __forceinline__ void br1n_body(const uint16_t *__restrict__ clue_a, c
       for (int e = 0; e < 16; ++e) ac[out][e] = canon<M>(ac[out][e] + o[out][e]);
     }
   }
-  if (mode == 0) {  // extract_lwe_locally (coefficient 0), detector.rs:561
-#pragma unroll
-    for (int e = 0; e < 16; ++e) st[lane + 64 * e] = (int)ac[0][e];
-    Ntt1W::wave_sync();
-    uint32_t *o = ext + g * (N1 + 1);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int j = lane + 64 * e;
-      o[j] = Lvl1Int::to_u32(j == 0 ? st[0] : -st[N1 - j]);
-    }
-    if (lane == 0) o[N1] = Lvl1Int::to_u32((int)ac[1][0]);
-  } else {
-    uint64_t *o = rlwe_out + g * 2 * N1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      o[lane + 64 * e] = Lvl1Int::to_u32((int)ac[0][e]);
-      o[N1 + lane + 64 * e] = Lvl1Int::to_u32((int)ac[1][e]);
-    }
-  }
+  lvl1_store_wave([&](int p, int e) { return (int)ac[p][e]; }, st, g, mode, ext, rlwe_out, lane);
 }
 
 __global__ __launch_bounds__(64) void br1n_kernel(const uint16_t *__restrict__ clue_a,

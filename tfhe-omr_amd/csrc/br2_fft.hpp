@@ -634,7 +634,6 @@ __global__ __launch_bounds__(BR2Y_T, 1) void br2y_kernel(const uint32_t *__restr
   const int r = row, wid = 2 * m + r;
   const int g = __builtin_amdgcn_readfirstlane((int)threadIdx.x / T), t = (int)threadIdx.x % T;
   const int pslot = __builtin_amdgcn_readfirstlane(wid < 2 ? 8 + 8 * wid + (int)(threadIdx.x >> 6) : -1);
-  (void)pslot;
   OMR_PHASE_CLOCK(pslot, 0);
   const uint32_t *lwe = lwe_int + (size_t)m * (NI + 1);
   if (g == 0) F::load_twiddles(tws, twg, t);

@@ -52,8 +52,7 @@ __device__ __forceinline__ void cmux_decompose(double *st, bool stage, const dou
 #pragma unroll
   for (int e = 0; e < E; ++e)
     Digits2::pack(canon_small<M>(rot_read_lds<N>(st, t + e * T, a) - (OWN ? acc[e] : st[t + e * T])), pk[e]);
-  __builtin_amdgcn_wave_barrier();
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  wave_lds_fence();
 }
 
 // The digit loop: digits first .. first + COUNT - 1 of pk in order (the throughput kernel's
@@ -212,7 +211,6 @@ __global__ __launch_bounds__(BR2L_T, 1) void br2x_kernel(const uint32_t *__restr
   }
   uint32_t hc = 0;  // hand-offs so far (executed steps)
   const int pslot = __builtin_amdgcn_readfirstlane(blockIdx.x < 2 ? 8 + 8 * (int)blockIdx.x + (int)(threadIdx.x >> 6) : -1);
-  (void)pslot;
   OMR_PHASE_CLOCK(pslot, 0);
 #pragma unroll 1
   for (int i = 0; i < NI; ++i) {

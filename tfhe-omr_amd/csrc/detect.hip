@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 
+#include "br1_fft.hpp"
 #include "br1_latency.hpp"
 #include "br1_ntt.hpp"
 #include "br2_fft.hpp"

@@ -26,18 +26,6 @@
 
 namespace omr {
 
-// LDS visibility within one wave: this wave's LDS writes have landed, and the compiler moves no
-// memory operation across (waves of a workgroup stay independent).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-}
-// Compiler-only ordering of one wave's LDS accesses (its LDS operations complete in order).
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_wave_barrier();
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-}
 // forward radix-2 butterfly in tangent form: (p, q) <- (p + w q, p - w q), w = c (1 + i t);
 // I: the node's twiddle is i w
 template <bool I>

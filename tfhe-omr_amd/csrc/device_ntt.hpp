@@ -9,6 +9,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "lds_sync.hpp"
 
 namespace omr {
 
@@ -16,16 +17,6 @@ namespace omr {
 // 32..63 of a <-> lanes 0..31 of b, v_permlane32_swap; 4: odd 16-lane rows of a <-> even rows of
 // b, v_permlane16_swap): afterwards a holds the lane-bit-0 half and lane bit LB indexes the old
 // register bit. One instruction per dword pair.
-// Workgroup barrier for LDS traffic only: this wave's LDS reads / writes are done, then s_barrier.
-// Unlike __syncthreads() (a workgroup-scope fence: s_waitcnt vmcnt(0) lgkmcnt(0)) it leaves the
-// wave's global loads in flight across the barrier (cdna_hip_programming.md, "Pipelining across
-// barriers"); callers that hand global data between waves must not use it.
-__device__ __forceinline__ void wg_barrier_lds() {
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_s_barrier();
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-}
-
 template <int LB>
 __device__ __forceinline__ void swap_lane_bit(double &a, double &b) {
   static_assert(LB == 4 || LB == 5, "lane bits 4 and 5 have swap instructions");
@@ -156,11 +147,6 @@ struct WgNtt {
       if ((thread_of(pf, idx) >> 6) != (thread_of(pt, idx) >> 6)) return false;
     return true;
   }
-  __device__ static __forceinline__ void wave_sync() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes have landed
-    __builtin_amdgcn_wave_barrier();
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  }
 
   // Exchange PF -> PT, the ORD-th of its transform; LAST: no further exchange follows (a
   // workgroup barrier then protects the buffers for whatever the caller does next).
@@ -176,7 +162,7 @@ struct WgNtt {
 #pragma unroll
       for (int e = 0; e < E; ++e) buf[c * N + pad(index(PF, tid, e))] = x[c][e];
     if constexpr (WL)
-      wave_sync();
+      wave_lds_sync();
     else
       __syncthreads();
 #pragma unroll
@@ -185,7 +171,7 @@ struct WgNtt {
       for (int e = 0; e < E; ++e) x[c][e] = buf[c * N + pad(index(PT, tid, e))];
     if constexpr (LAST) {
       if constexpr (!LAST && WL)
-        wave_sync();
+        wave_lds_sync();
       else
         __syncthreads();
     }
@@ -417,8 +403,7 @@ struct CmuxNtt {
     wg_barrier_lds();  // LDS only: the caller's key loads stay in flight across the exchange
 #pragma unroll
     for (int e = 0; e < E; ++e) x[e] = buf[cmux_idx(PT, tid, e)];
-    __builtin_amdgcn_wave_barrier();  // keep the next writes below these reads (in-order LDS)
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    wave_lds_fence();  // keep the next writes below these reads (in-order LDS)
   }
   // wave-local exchange P1 <-> P2 through W
   template <int PF, int PT>
@@ -426,11 +411,10 @@ struct CmuxNtt {
     double *buf = lds + 2 * N;
 #pragma unroll
     for (int e = 0; e < E; ++e) buf[padw(cmux_idx(PF, tid, e))] = x[e];
-    G::wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int e = 0; e < E; ++e) x[e] = buf[padw(cmux_idx(PT, tid, e))];
-    __builtin_amdgcn_wave_barrier();
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    wave_lds_fence();
   }
   // P2 <-> P3: register bit 2 <-> lane bit 5, register bit 1 <-> lane bit 4 (an involution)
   __device__ static __forceinline__ void swap23(double (&x)[E]) {

@@ -165,21 +165,17 @@ struct Fft1024 {
     const int bw = swz(S, idx(PF, t, 0)), br = swz(S, idx(PT, t, 0));
 #pragma unroll
     for (int e = 0; e < E; ++e) buf[slot_of<S, PF>(bw, e)] = make_double2(xr[e], xi[e]);
-    if constexpr (CROSS) {
+    if constexpr (CROSS)
       wg_barrier_lds();  // global loads (the next key blocks) stay in flight
-    } else {
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-      __builtin_amdgcn_wave_barrier();
-      __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    }
+    else
+      wave_lds_sync();
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const double2 v = buf[slot_of<S, PT>(br, e)];
       xr[e] = v.x;
       xi[e] = v.y;
     }
-    __builtin_amdgcn_wave_barrier();  // the next writes stay below these reads (in-order LDS per wave)
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    wave_lds_fence();  // the next writes stay below these reads (in-order LDS per wave)
   }
   // forward radix-4 pass in tangent form (device_fft.hpp, bfly): the tree's stage A on the pairs
   // (0, 2), (1, 3), then B on (0, 1) and i B on (2, 3) -- the same map as "T = (1, B, A, AB), then
