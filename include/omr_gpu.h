@@ -138,6 +138,64 @@ omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const uint64_t *
                                  uint16_t *payloads);
 
 /* ---------------------------------------------------------------------------------------
+ * Auditor (client side, GPU or CPU): decrypt, classify and noise-audit NttRlweCiphertexts
+ * (pertinency vectors or digests) under the pack's s2. The decoded plaintexts are those of
+ * omr_decrypt_decode (retriever.rs:84-96); the class per ciphertext is the omd KAT (omd.rs:48-58:
+ * a pertinent message decrypts to [1, 0, .., 0], any other to zeros); the residual summary is the
+ * exact-integer counterpart of NoiseSigmaInfo (retriever.rs:390-560).
+ *
+ * Arithmetic, exact integers throughout. Input words are reduced mod q2 first. For one ciphertext
+ * (a, b) the phase is c = N2^-1 * INTT(b - a (.) NTT(s2)) mod q2, canonical in [0, q2). Per
+ * coefficient, with p = 257:
+ *   t' = floor((2 p c + q2) / (2 q2)) in [0, 257]; the decoded value is t = 0 if t' = 257, else t';
+ *   the residual is r = p c - t' q2, |r| <= (q2 - 1) / 2 < 2^49.
+ * |r| / q2 is the distance of the phase from its decode point in plaintext steps: 0.5 would be a
+ * decode failure. An encoder places plaintext m at m * Delta2, Delta2 = round_half_up(q2 / 257), and
+ * 257 * Delta2 - q2 = -69, so a noiseless encryption of m has r = -69 m (at most 69 * 256 in
+ * magnitude): that systematic term is part of r by definition.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  uint64_t max_abs_residual; /* largest |r| over the 2,048 coefficients */
+  uint32_t nonzero;          /* decoded coefficients != 0 */
+  uint32_t first;            /* decoded coefficient 0 */
+} omr_ct_audit;
+/* Class of a record: zero (nonzero == 0), one-hot (nonzero == 1 && first == 1: the omd KAT's
+ * [1, 0, .., 0]), other (anything else). */
+#define OMR_AUDIT_RESIDUAL_BINS 50
+/* Accumulated into by every audit call that is given one, never reset by the library (the caller
+ * zeroes it). Only integer counts and a maximum, so it does not depend on grid, staging or call
+ * order. residual_bits[k] counts the coefficients whose |r| has bit length k (k = 0 for r = 0; k <= 49);
+ * their sum is 2048 * ciphertexts. */
+typedef struct {
+  uint64_t ciphertexts, zero, one_hot, other, max_abs_residual;
+  uint64_t residual_bits[OMR_AUDIT_RESIDUAL_BINS];
+} omr_audit_summary;
+
+/* An auditor holds the pack's level-2 secret (NTT(s2)) and the inverse twiddles on `device`; it needs
+ * no detector context: the party that holds the secret is not the detector. Calls on one auditor are
+ * serialised. */
+typedef struct omr_auditor omr_auditor;
+omr_status omr_auditor_create(const omr_secret_key_pack *sk, int device, omr_auditor **out);
+void       omr_auditor_destroy(omr_auditor *aud);
+/* knobs, results identical for every setting: workgroups of the grid (0 = default, two per compute
+ * unit) and the ciphertexts staged per piece by the host entry point (0 = default 2,048 = 64 MiB) */
+omr_status omr_auditor_set_grid(omr_auditor *aud, unsigned workgroups);
+omr_status omr_auditor_set_staging(omr_auditor *aud, size_t max_ciphertexts);
+/* device buffers of the auditor's device, enqueued on hip_stream (NULL = null stream), returns once
+ * enqueued; d_cts u64 [n][2][2048] (16-byte aligned), d_records [n], d_decoded u16 [n][2048],
+ * d_summary (added into; the caller zeroes it): any may be NULL, not all three; n = 0 does nothing */
+omr_status omr_audit_device(omr_auditor *aud, const uint64_t *d_cts, size_t n, omr_ct_audit *d_records,
+                            uint16_t *d_decoded, omr_audit_summary *d_summary, void *hip_stream);
+/* host buffers, staged in pieces; returns when done; summary is added into */
+omr_status omr_audit(omr_auditor *aud, const uint64_t *cts, size_t n, omr_ct_audit *records,
+                     uint16_t *decoded, omr_audit_summary *summary);
+/* the same results on the CPU (no GPU, no auditor): the statement the kernel is checked against and
+ * the path of a client without a device. nthreads <= 0: the host's cores, at most 16. */
+omr_status omr_audit_cpu(const omr_secret_key_pack *sk, const uint64_t *cts, size_t n,
+                         omr_ct_audit *records, uint16_t *decoded, omr_audit_summary *summary,
+                         int nthreads);
+
+/* ---------------------------------------------------------------------------------------
  * Detector — one context per GPU; calls on one context are serialised; contexts are
  * independent. Detector::new (detector.rs:85-110) uploads the keys and converts them to the
  * device layout; the LUTs (:457-503) are built inside. The key view may point to host memory

@@ -7,6 +7,8 @@
 //! `encode_pertinent_payloads`), [`SecretKeyPack`] for `KeyGen::generate_secret_key` /
 //! `SecretKeyPack` (`key_gen/secret.rs:46-209`) with seeded streams, [`RetrievalParams`]
 //! (`parameters/retrieval_params.rs:50-106`) and [`Retriever`] (`retriever.rs:188-260`).
+//! [`Auditor`] decrypts, classifies and noise-audits ciphertexts on the device (the counterpart of
+//! `NoiseSigmaInfo`, `retriever.rs:390-560`).
 //! [`DigestSession`] runs the whole board flow (`examples/omr.rs:160-203`) inside the library
 //! without a pertinency vector on the caller's side.
 //!
@@ -21,7 +23,7 @@
 
 use std::ffi::CStr;
 use std::fmt;
-use std::os::raw::{c_char, c_int, c_long, c_void};
+use std::os::raw::{c_char, c_int, c_long, c_uint, c_void};
 use std::time::Duration;
 
 /// Raw bindings of `include/omr_gpu.h`, one declaration per C entry point.
@@ -61,6 +63,36 @@ pub mod ffi {
     #[repr(C)]
     pub struct OmrDigest {
         _private: [u8; 0],
+    }
+    #[repr(C)]
+    pub struct OmrAuditor {
+        _private: [u8; 0],
+    }
+    pub const OMR_AUDIT_RESIDUAL_BINS: usize = 50;
+    /// `omr_ct_audit`: the record that classifies one ciphertext.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct OmrCtAudit {
+        pub max_abs_residual: u64,
+        pub nonzero: u32,
+        pub first: u32,
+    }
+    /// `omr_audit_summary`: integer tallies that every audit call adds into.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub struct OmrAuditSummary {
+        pub ciphertexts: u64,
+        pub zero: u64,
+        pub one_hot: u64,
+        pub other: u64,
+        pub max_abs_residual: u64,
+        pub residual_bits: [u64; OMR_AUDIT_RESIDUAL_BINS],
+    }
+    impl Default for OmrAuditSummary {
+        fn default() -> Self {
+            Self { ciphertexts: 0, zero: 0, one_hot: 0, other: 0, max_abs_residual: 0,
+                   residual_bits: [0; OMR_AUDIT_RESIDUAL_BINS] }
+        }
     }
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -139,6 +171,19 @@ pub mod ffi {
                                      all_payloads_count: usize, combination_count: u32, weights: *const u16,
                                      indices: *const usize,
                                      n_indices: usize, payloads: *mut u16) -> OmrStatus;
+
+        // auditor (omd.rs:48-58 KAT and NoiseSigmaInfo, retriever.rs:390-560, in exact integers)
+        pub fn omr_auditor_create(sk: *const OmrSecretKeyPack, device: c_int, out: *mut *mut OmrAuditor) -> OmrStatus;
+        pub fn omr_auditor_destroy(aud: *mut OmrAuditor);
+        pub fn omr_auditor_set_grid(aud: *mut OmrAuditor, workgroups: c_uint) -> OmrStatus;
+        pub fn omr_auditor_set_staging(aud: *mut OmrAuditor, max_ciphertexts: usize) -> OmrStatus;
+        pub fn omr_audit_device(aud: *mut OmrAuditor, d_cts: *const u64, n: usize, d_records: *mut OmrCtAudit,
+                                d_decoded: *mut u16, d_summary: *mut OmrAuditSummary,
+                                hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_audit(aud: *mut OmrAuditor, cts: *const u64, n: usize, records: *mut OmrCtAudit,
+                         decoded: *mut u16, summary: *mut OmrAuditSummary) -> OmrStatus;
+        pub fn omr_audit_cpu(sk: *const OmrSecretKeyPack, cts: *const u64, n: usize, records: *mut OmrCtAudit,
+                             decoded: *mut u16, summary: *mut OmrAuditSummary, nthreads: c_int) -> OmrStatus;
 
         // detector (detector.rs:85-453)
         pub fn omr_ctx_create(key: *const OmrDetectionKeyView, device: c_int, out: *mut *mut OmrCtx) -> OmrStatus;
@@ -686,6 +731,107 @@ impl<'a> Retriever<'a> {
             })
             .collect();
         Ok((found_buf, payloads))
+    }
+}
+
+/// Class of an audited ciphertext (`omr_ct_audit`): all zeros, `[1, 0, .., 0]` (the omd KAT of a
+/// pertinent message, omd.rs:48-58), or anything else.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum AuditClass {
+    Zero,
+    OneHot,
+    Other,
+}
+
+impl OmrCtAudit {
+    pub fn class(&self) -> AuditClass {
+        match (self.nonzero, self.first) {
+            (0, _) => AuditClass::Zero,
+            (1, 1) => AuditClass::OneHot,
+            _ => AuditClass::Other,
+        }
+    }
+    /// Distance of the worst coefficient from its decode point in plaintext steps (0.5: a failure).
+    pub fn max_residual(&self) -> f64 {
+        self.max_abs_residual as f64 / OMR_Q2 as f64
+    }
+}
+
+/// What an audit returns: one record and 2,048 decoded values mod 257 per ciphertext, and the
+/// summary the call added into.
+pub struct Audit {
+    pub records: Vec<OmrCtAudit>,
+    pub decoded: Vec<u16>,
+    pub summary: OmrAuditSummary,
+}
+
+/// The auditor (`omr_auditor`): the level-2 secret on one device. Decrypts, classifies and
+/// noise-audits `NttRlwe` ciphertexts (pertinency vectors, digests) on the GPU: the counterpart of
+/// the reference's `NoiseSigmaInfo` (retriever.rs:390-560) in exact integers. The borrow keeps the
+/// pack alive for `audit_cpu`.
+pub struct Auditor<'a> {
+    raw: *mut OmrAuditor,
+    secret: &'a SecretKeyPack,
+}
+// Calls on one auditor are serialised inside the library.
+unsafe impl Send for Auditor<'_> {}
+unsafe impl Sync for Auditor<'_> {}
+
+impl<'a> Auditor<'a> {
+    pub fn new(secret: &'a SecretKeyPack, device: i32) -> Result<Self, OmrError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { omr_auditor_create(secret.raw, device, &mut raw) })?;
+        Ok(Self { raw, secret })
+    }
+
+    /// Workgroups of the kernel's grid (0 = default); the results do not depend on it.
+    pub fn set_grid(&self, workgroups: u32) -> Result<(), OmrError> {
+        check(unsafe { omr_auditor_set_grid(self.raw, workgroups as c_uint) })
+    }
+
+    /// Ciphertexts staged per piece by `audit` (0 = default 2,048); the results do not depend on it.
+    pub fn set_staging(&self, max_ciphertexts: usize) -> Result<(), OmrError> {
+        check(unsafe { omr_auditor_set_staging(self.raw, max_ciphertexts) })
+    }
+
+    /// Host ciphertexts through the device (`omr_audit`), added into `summary`.
+    pub fn audit(&self, cts: &[NttRlwe], summary: &mut OmrAuditSummary) -> Result<Audit, OmrError> {
+        let flat = NttRlwe::flatten(cts);
+        let mut records = vec![OmrCtAudit::default(); cts.len()];
+        let mut decoded = vec![0u16; cts.len() * OMR_N2];
+        check(unsafe {
+            omr_audit(self.raw, flat.as_ptr(), cts.len(), records.as_mut_ptr(), decoded.as_mut_ptr(), summary)
+        })?;
+        Ok(Audit { records, decoded, summary: *summary })
+    }
+
+    /// The same results on the CPU (`omr_audit_cpu`), on `nthreads` host threads (0: all, at most 16).
+    pub fn audit_cpu(&self, cts: &[NttRlwe], summary: &mut OmrAuditSummary, nthreads: i32) -> Result<Audit, OmrError> {
+        let flat = NttRlwe::flatten(cts);
+        let mut records = vec![OmrCtAudit::default(); cts.len()];
+        let mut decoded = vec![0u16; cts.len() * OMR_N2];
+        check(unsafe {
+            omr_audit_cpu(self.secret.raw, flat.as_ptr(), cts.len(), records.as_mut_ptr(), decoded.as_mut_ptr(),
+                          summary, nthreads)
+        })?;
+        Ok(Audit { records, decoded, summary: *summary })
+    }
+
+    /// Device buffers of the auditor's GPU (`omr_audit_device`): returns once enqueued on `hip_stream`.
+    ///
+    /// # Safety
+    /// `d_cts` must be device memory of `n` ciphertexts (u64 `[n][2][2048]`, 16-byte aligned); each
+    /// output pointer is null or device memory of `n` records, `n * 2048` values, one summary (zeroed
+    /// by the caller); not all three null. All must stay valid until the stream has run the work.
+    pub unsafe fn audit_device(&self, d_cts: *const u64, n: usize, d_records: *mut OmrCtAudit, d_decoded: *mut u16,
+                               d_summary: *mut OmrAuditSummary, hip_stream: *mut c_void) -> Result<(), OmrError> {
+        check(omr_audit_device(self.raw, d_cts, n, d_records, d_decoded, d_summary, hip_stream))
+    }
+}
+
+impl Drop for Auditor<'_> {
+    fn drop(&mut self) {
+        unsafe { omr_auditor_destroy(self.raw) }
     }
 }
 

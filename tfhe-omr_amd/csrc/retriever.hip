@@ -2,32 +2,62 @@
 // decode_pertinent_indices (:63-130), decode_combined_payloads (:318-362) and
 // solve_matrix_mod_257 (matrix.rs:164-247). Used by clients of the detector, by bench.py's
 // end-to-end check and by the multi-GPU driver; needs only the secret key pack.
+#include <mutex>
 #include <set>
 #include <string>
 #include <vector>
 
+#include "audit_decode.hpp"
 #include "host_ring.hpp"
 
 using namespace omr;
 
 namespace {
 
-// b - a * NTT(s2) in the NTT domain, inverse NTT, round(c * p / q2) half up, mod p
-// (retriever.rs:84-96). ct: u64 [2][N2] (a, b), NTT domain.
-void decrypt_decode_one(const omr_secret_key_pack *sk, const uint64_t *ct, uint32_t p, uint32_t *out) {
+// The phase of one ciphertext: N2^-1 INTT(b - a * NTT(s2)), canonical in [0, q2) (retriever.rs:84-96).
+// ct: u64 [2][N2] (a, b), NTT domain, any u64 words (reduced mod q2 first).
+void phase_one(const omr_secret_key_pack *sk, const uint64_t *ct, uint64_t *ph) {
   const HostNtt &T = ntt2();
-  std::vector<uint64_t> ph(N2);
   const uint64_t *a = ct, *b = ct + N2;
   for (int j = 0; j < N2; ++j) {
     const uint64_t as = T.mul(a[j] % Q2, sk->s2_ntt[j], sk->s2_ntts[j]);
     const uint64_t bj = b[j] % Q2;
     ph[j] = bj >= as ? bj - as : bj + Q2 - as;
   }
-  T.inv(ph.data());
+  T.inv(ph);
+}
+
+// round(c * p / q2) half up, mod p, of the phase (retriever.rs:84-96).
+void decrypt_decode_one(const omr_secret_key_pack *sk, const uint64_t *ct, uint32_t p, uint32_t *out) {
+  std::vector<uint64_t> ph(N2);
+  phase_one(sk, ct, ph.data());
   for (int j = 0; j < N2; ++j) {
     uint64_t t = (uint64_t)(((u128)ph[j] * (2 * p) + Q2) / ((u128)2 * Q2));
     out[j] = (uint32_t)(t >= p ? t - p : t);
   }
+}
+
+// The auditor's results for one ciphertext (include/omr_gpu.h, "Auditor"): its record, optionally its
+// decoded values, and its tallies added into `sum`.
+omr_ct_audit audit_one(const omr_secret_key_pack *sk, const uint64_t *ct, uint16_t *decoded, omr_audit_summary &sum) {
+  std::vector<uint64_t> ph(N2);
+  phase_one(sk, ct, ph.data());
+  omr_ct_audit rec{0, 0, 0};
+  for (int j = 0; j < N2; ++j) {
+    const DecodedCoeff d = decode_coeff(ph[j]);
+    if (decoded) decoded[j] = (uint16_t)d.t;
+    if (j == 0) rec.first = d.t;
+    rec.nonzero += d.t != 0;
+    rec.max_abs_residual = std::max(rec.max_abs_residual, d.abs_r);
+    ++sum.residual_bits[bit_length(d.abs_r)];
+  }
+  const bool zero = rec.nonzero == 0, one_hot = rec.nonzero == 1 && rec.first == 1;
+  ++sum.ciphertexts;
+  sum.zero += zero;
+  sum.one_hot += one_hot;
+  sum.other += !zero && !one_hot;
+  sum.max_abs_residual = std::max(sum.max_abs_residual, rec.max_abs_residual);
+  return rec;
 }
 
 }  // namespace
@@ -37,6 +67,26 @@ extern "C" omr_status omr_decrypt_decode(const omr_secret_key_pack *sk, const ui
   if (!sk || (n && (!ct || !out)))
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_decrypt_decode: NULL argument");
   parallel_for(n, 0, [&](size_t m) { decrypt_decode_one(sk, ct + m * 2 * N2, P, out + m * N2); });
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_audit_cpu(const omr_secret_key_pack *sk, const uint64_t *cts, size_t n,
+                                    omr_ct_audit *records, uint16_t *decoded, omr_audit_summary *summary,
+                                    int nthreads) {
+  if (!sk) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_audit_cpu: NULL secret key pack");
+  if (!records && !decoded && !summary) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_audit_cpu: no output requested");
+  if (n == 0) return OMR_OK;
+  if (!cts) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_audit_cpu: NULL ciphertexts");
+  std::mutex mu;  // guards *summary: integer tallies, so the order of the merges does not matter
+  parallel_for(n, nthreads, [&](size_t m) {
+    omr_audit_summary one{};
+    const omr_ct_audit rec = audit_one(sk, cts + m * 2 * N2, decoded ? decoded + m * N2 : nullptr, one);
+    if (records) records[m] = rec;
+    if (summary) {
+      std::lock_guard<std::mutex> lk(mu);
+      merge_summary(*summary, one);
+    }
+  });
   return OMR_OK;
 }
 

@@ -4,10 +4,13 @@
 // encode_pertinent_payloads, client-side retrieval, and a check that exactly the pertinent
 // indices and their payloads come back.
 //
-//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--host-only]
+//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
+// --audit checks the detector's output on the GPU with the recipient's secret (omr_audit): every pertinent
+// message's ciphertext must decrypt to [1, 0, .., 0], every other one to zeros (with --session there is
+// no pertinency vector to audit), and the digests' decode residuals are reported.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -48,15 +51,18 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
+  bool audit = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if ((a == "-p" || a == "--payload-count") && i + 1 < argc) D = std::max<size_t>(1, std::stoull(argv[++i]));
     else if ((a == "-d" || a == "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
     else if ((a == "-s" || a == "--seed") && i + 1 < argc) seed = std::stoull(argv[++i]);
     else if (a == "--session" && i + 1 < argc) session_piece = std::max<size_t>(1, std::stoull(argv[++i]));
+    else if (a == "--audit") audit = true;
     else if (a == "--host-only") host_only = true;
     else {
-      std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--host-only]\n",
+      std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] "
+                   "[--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -121,6 +127,10 @@ int main(int argc, char **argv) {
   omr_detection_key_view view{bsk1.data(), ksk.data(), bsk2.data(), tk.data()};
   CHECK(omr_ctx_create(&view, device, &ctx));
   const uint32_t n_idx = rp.max_encode_indices_cipher_count, n_pay = rp.cmb_cipher_count;
+  omr_auditor *aud = nullptr;
+  if (audit) CHECK(omr_auditor_create(pa, device, &aud));
+  int audit_fails = 0;
+  omr_audit_summary pv_sum{}, dg_sum{};
   std::vector<uint64_t> idx_ct((size_t)n_idx * 2 * N2), pay_ct((size_t)n_pay * 2 * N2);
   if (session_piece) {
     // the same flow inside the library, piece by piece (omr_digest_*): detect + both encoders
@@ -149,6 +159,20 @@ int main(int argc, char **argv) {
     CHECK(omr_detect_batch(ctx, ca.data(), cb.data(), D, pv.data()));
     const double td = secs(t);
     std::printf("detect time: %.3f s (%.3f ms per message, host buffers)\n", td, td * 1e3 / D);
+    if (audit) {
+      // the omd KAT over the whole board: one-hot exactly where pertinent, zeros elsewhere
+      std::vector<omr_ct_audit> rec(D);
+      CHECK(omr_audit(aud, pv.data(), D, rec.data(), nullptr, &pv_sum));
+      for (size_t m = 0; m < D; ++m) {
+        const bool one_hot = rec[m].nonzero == 1 && rec[m].first == 1, zero = rec[m].nonzero == 0;
+        if (is_pert[m] ? !one_hot : !zero) {
+          if (!audit_fails) std::printf("Fail: message %zu (%s) decrypts to %u non-zero coefficients, first %u\n", m,
+                                        is_pert[m] ? "pertinent" : "not pertinent", rec[m].nonzero, rec[m].first);
+          ++audit_fails;
+        }
+      }
+      if (pv_sum.other || pv_sum.one_hot != pert_count || pv_sum.zero != D - pert_count) ++audit_fails;
+    }
 
     // encode_pertinent_indices x max_encode_indices_cipher_count, encode_pertinent_payloads
     t = clk::now();
@@ -159,6 +183,17 @@ int main(int argc, char **argv) {
     CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
                               rp.cmb_count_per_cipher, pay_ct.data()));
     std::printf("encode pertinent payloads time: %.3f s\n", secs(t));
+  }
+
+  if (audit) {
+    CHECK(omr_audit(aud, idx_ct.data(), n_idx, nullptr, nullptr, &dg_sum));
+    CHECK(omr_audit(aud, pay_ct.data(), n_pay, nullptr, nullptr, &dg_sum));
+    std::printf("audit: pertinency vector %llu one-hot, %llu zero, %llu other, max |r|/q2 %.3e; digests %llu "
+                "ciphertexts, max |r|/q2 %.3e%s\n",
+                (unsigned long long)pv_sum.one_hot, (unsigned long long)pv_sum.zero, (unsigned long long)pv_sum.other,
+                (double)pv_sum.max_abs_residual / (double)OMR_Q2, (unsigned long long)dg_sum.ciphertexts,
+                (double)dg_sum.max_abs_residual / (double)OMR_Q2, audit_fails ? " -- FAILED" : "");
+    omr_auditor_destroy(aud);
   }
 
   // Retriever::decode_digest (omr.rs:216-218)
@@ -172,7 +207,7 @@ int main(int argc, char **argv) {
                               solved.data()));
   std::printf("decode time: %.3f s\n", secs(t));
 
-  int fails = found == pert ? 0 : 1;
+  int fails = (found == pert ? 0 : 1) + audit_fails;
   if (fails) std::printf("Fail: %zu indices recovered, %zu pertinent\n", found.size(), pert.size());
   for (size_t k = 0; k < found.size() && !fails; ++k)
     if (!std::equal(&solved[k * PAYLOAD], &solved[(k + 1) * PAYLOAD], &payloads[found[k] * PAYLOAD])) {

@@ -61,6 +61,17 @@ class _DigestInfo(C.Structure):
                 ("pv_capacity_messages", C.c_size_t)]
 
 
+class _AuditSummary(C.Structure):
+    """omr_audit_summary."""
+    _fields_ = [(n, C.c_uint64) for n in ("ciphertexts", "zero", "one_hot", "other", "max_abs_residual")] + \
+               [("residual_bits", C.c_uint64 * 50)]
+
+
+# omr_ct_audit as a structured dtype (16 bytes)
+AUDIT_RECORD = np.dtype([("max_abs_residual", np.uint64), ("nonzero", np.uint32), ("first", np.uint32)])
+AUDIT_RESIDUAL_BINS = 50
+
+
 EXPORTS = {
     "omr_last_error": (C.c_char_p, []),
     "omr_version": (C.c_char_p, []),
@@ -124,6 +135,14 @@ EXPORTS = {
     "omr_retrieve_payloads": (C.c_int, [C.c_void_p, _u64p, C.c_uint32, C.c_size_t, C.c_uint32, _u16p,
                                         np.ctypeslib.ndpointer(dtype=np.uintp, flags="C_CONTIGUOUS"),
                                         C.c_size_t, _u16p]),
+    "omr_auditor_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "omr_auditor_destroy": (None, [C.c_void_p]),
+    "omr_auditor_set_grid": (C.c_int, [C.c_void_p, C.c_uint]),
+    "omr_auditor_set_staging": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "omr_audit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "omr_audit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_audit_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "omr_second_level": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_blind_rotate_level2": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_ntt": (C.c_int, [C.c_int, C.c_int, _u64p, C.c_size_t, C.c_int]),
@@ -383,6 +402,95 @@ class Retriever:
         indices = self.decode_pertinent_indices(idx_cts)
         weights = payload_weights(seed, self.params)
         return indices, self.decode_combined_payloads_and_solve(pay_cts, weights, indices)
+
+
+def _summary_dict(t: "_AuditSummary") -> dict:
+    d = {n: int(getattr(t, n)) for n in ("ciphertexts", "zero", "one_hot", "other", "max_abs_residual")}
+    d["residual_bits"] = np.array(t.residual_bits[:], dtype=np.uint64)
+    return d
+
+
+def audit_classes(records):
+    """(zero, one_hot, other) index arrays of audit records: zero has no decoded coefficient != 0,
+    one-hot decodes to [1, 0, .., 0] (the omd KAT of a pertinent message), other is anything else."""
+    r = np.asarray(records)
+    zero = r["nonzero"] == 0
+    one_hot = (r["nonzero"] == 1) & (r["first"] == 1)
+    return np.nonzero(zero)[0], np.nonzero(one_hot)[0], np.nonzero(~zero & ~one_hot)[0]
+
+
+def _audit_host(call, what, cts):
+    cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, N2)
+    n = cts.shape[0]
+    records = np.zeros(n, AUDIT_RECORD)
+    decoded = np.zeros((n, N2), np.uint16)
+    t = _AuditSummary()
+    _check(call(cts.ctypes.data, n, records.ctypes.data, decoded.ctypes.data, C.addressof(t)), what)
+    return records, decoded, _summary_dict(t)
+
+
+def audit_cpu(secret: "SecretKeyPack", cts, nthreads: int = 0):
+    """omr_audit_cpu: (records [n] of AUDIT_RECORD, decoded u16 [n][2048], summary dict) of
+    NttRlweCiphertexts u64 [n][2][2048] under the pack's s2, on the CPU (no GPU, no auditor)."""
+    return _audit_host(lambda c, n, r, d, s: lib().omr_audit_cpu(secret._h, c, n, r, d, s, nthreads),
+                       "omr_audit_cpu", cts)
+
+
+class Auditor:
+    """omr_auditor: the level-2 secret on one device; decrypts, classifies and noise-audits
+    NttRlweCiphertexts (pertinency vectors, digests) on the GPU. The counterpart of the reference's
+    NoiseSigmaInfo (retriever.rs:390-560) and of the omd KAT (omd.rs:48-58), in exact integers."""
+
+    classes = staticmethod(audit_classes)
+
+    def __init__(self, pack: "SecretKeyPack", device: int = 0):
+        h = C.c_void_p()
+        _check(lib().omr_auditor_create(pack._h, device, C.byref(h)), "omr_auditor_create")
+        self._h = h
+        self._destroy = lib().omr_auditor_destroy
+        self._sk = pack
+        self.device = device
+
+    def set_grid(self, workgroups: int = 0):
+        _check(lib().omr_auditor_set_grid(self._h, workgroups), "omr_auditor_set_grid")
+
+    def set_staging(self, max_ciphertexts: int = 0):
+        _check(lib().omr_auditor_set_staging(self._h, max_ciphertexts), "omr_auditor_set_staging")
+
+    def audit(self, cts):
+        """Host ciphertexts u64 [n][2][2048] through the device (omr_audit): (records, decoded, summary)."""
+        return _audit_host(lambda c, n, r, d, s: lib().omr_audit(self._h, c, n, r, d, s), "omr_audit", cts)
+
+    def audit_cpu(self, cts, nthreads: int = 0):
+        """The same results from omr_audit_cpu."""
+        return audit_cpu(self._sk, cts, nthreads)
+
+    def audit_device(self, d_cts: int, n: int, d_records: int = 0, d_decoded: int = 0, d_summary: int = 0,
+                     stream: int = 0) -> None:
+        """Device pointers (omr_audit_device): d_records [n] of 16-byte records, d_decoded u16 [n][2048],
+        d_summary 440 bytes that are added into (the caller zeroes them); 0 skips an output. Enqueued
+        on `stream`; the caller synchronises."""
+        _check(lib().omr_audit_device(self._h, d_cts, n, d_records or None, d_decoded or None, d_summary or None,
+                                      stream or None), "omr_audit_device")
+
+    @staticmethod
+    def summary_from_bytes(buf) -> dict:
+        """The dict form of an omr_audit_summary copied back from the device (440 bytes)."""
+        return _summary_dict(_AuditSummary.from_buffer_copy(bytes(buf)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 # Contexts still open at interpreter exit are destroyed by an atexit hook, which runs before the
