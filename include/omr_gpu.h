@@ -361,6 +361,54 @@ omr_status omr_encode_payloads_device(omr_ctx *ctx, const uint64_t *d_pv,
                                       void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Bitmap digest (none in the reference): the detection-only digest from which a recipient learns
+ * exactly which messages of a board are pertinent and how many, with no bound on the count known in
+ * advance and no bucket collisions. Retriever::decode_pertinent_indices (retriever.rs:63-130,
+ * :197-204) needs pertinent_count to know when it is done; this digest needs only the board size.
+ *
+ * Layout. A pertinent pv_g decrypts to [1, 0, .., 0] and any other to zeros (omd.rs:48-58), so
+ * pv_g * 2^t * X^j decrypts to 2^t at coefficient j. The message with global index g goes to
+ *   ciphertext c = g / 16384,  l = g % 16384,  coefficient j = l % 2048,  bit t = l / 2048,
+ * and a board of `all` messages has ceil(all / 16384) bitmap ciphertexts (omr_bitmap_ct_count):
+ *   out[c][h][i] = sum_g pv_g[h][i] * 2^t * psi^((2 brv11(i) + 1) j mod 4096)  mod q2,  h in {a, b},
+ * the second factor being NTT(X^j)[i] in the convention above. Outputs are canonical residues in the
+ * NTT domain like every digest; messages that are not folded in contribute nothing; the sum is exact,
+ * so every partition of a board into calls, added mod q2, gives the same bits. Coefficient j of
+ * ciphertext c decodes to sum_t 2^t [message 16384 c + 2048 t + j is pertinent] <= 255 < p.
+ *
+ * Noise condition. In the auditor's terms decoding is correct while |r| / q2 < 0.5 at every
+ * coefficient. Multiplying by 2^t X^j permutes and negates a ciphertext's noise coefficients and
+ * scales them by 2^t, so a full bitmap ciphertext's |r| / q2 is at most (sum_t 2^t) * 2048 * E =
+ * 522,240 E (plus the systematic term, at most 69 * 255 / q2), E being the largest |r| / q2 over the
+ * pertinency ciphertexts folded in: E < 9.5e-7 suffices (measured E and bitmap noise: DESIGN.md §1).
+ * ------------------------------------------------------------------------------------- */
+#define OMR_BITMAP_BITS 8
+#define OMR_BITMAP_MESSAGES_PER_CT 16384
+/* ceil(all_payloads_count / 16384); all_payloads_count = 0 (or a count beyond uint32_t) is invalid */
+omr_status omr_bitmap_ct_count(size_t all_payloads_count, uint32_t *n_ct);
+/* The bitmap ciphertexts of the whole board over the messages [global_offset, global_offset + D):
+ * d_out u64 [n_ct][2][2048], every ciphertext written (those the range does not touch are zero; D = 0
+ * writes zeros). d_pv u64 [D][2][2048], canonical (not validated), 16-byte aligned. Enqueued on
+ * hip_stream (NULL = null stream), returns once enqueued. A workgroup folds slices of 128 messages;
+ * omr_ctx_set_encode_chunks bounds the partials kept per ciphertext here too (identical bits). */
+omr_status omr_encode_bitmap_device(omr_ctx *ctx, const uint64_t *d_pv, size_t D, size_t global_offset,
+                                    size_t all_payloads_count, uint64_t *d_out /* [n_ct][2][2048] */,
+                                    void *hip_stream);
+/* The same on host buffers; returns when done. */
+omr_status omr_encode_bitmap(omr_ctx *ctx, const uint64_t *pv, size_t D, size_t global_offset,
+                             size_t all_payloads_count, uint64_t *out);
+/* Client side, host only: the global indices of the set bits of decoded bitmap ciphertexts (decoded
+ * u16 [n_ct][2048]: omr_decrypt_decode's values narrowed to u16, or the `decoded` output of omr_audit /
+ * omr_audit_cpu; a client with a GPU decodes the bitmap with the auditor), in increasing order. Writes
+ * at most cap indices and the full count to *found. OMR_ERR_INVALID_ARGUMENT ("not a bitmap digest of
+ * this board") for n_ct != omr_bitmap_ct_count(all), a value >= 256, or a set bit at or beyond all. */
+omr_status omr_bitmap_indices(const uint16_t *decoded /* [n_ct][2048] */, uint32_t n_ct,
+                              size_t all_payloads_count, size_t *indices, size_t cap, size_t *found);
+/* omr_decrypt_decode of the bitmap ciphertexts u64 [n_ct][2][2048] + omr_bitmap_indices (CPU). */
+omr_status omr_retrieve_bitmap(const omr_secret_key_pack *sk, const uint64_t *bitmap_cts, uint32_t n_ct,
+                               size_t all_payloads_count, size_t *indices, size_t cap, size_t *found);
+
+/* ---------------------------------------------------------------------------------------
  * Digest session — the detector's whole board flow (examples/omr.rs:160-203: detect every message,
  * encode_pertinent_indices per index ciphertext, encode_pertinent_payloads once; detector.rs:223-453)
  * behind one handle that never holds the board's pertinency vector. The caller feeds message
@@ -429,6 +477,22 @@ omr_status omr_digest_merge(omr_digest *dg, const uint64_t *idx_cts, const uint6
  * it returns OMR_ERR_DEVICE. */
 omr_status omr_digest_read(omr_digest *dg, uint64_t *idx_cts, uint64_t *pay_cts);
 omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info);
+/* The session's bitmap digest ("Bitmap digest" above). omr_digest_enable_bitmap allocates a zeroed
+ * running bitmap u64 [omr_bitmap_ct_count(all)][2][2048] on the device; every later piece then also folds
+ * its pertinency ciphertexts into it, in the same stream order and under the same poisoning rules as
+ * the index and payload digests, which are not affected. It must come before the session's first
+ * non-empty update and before any merge: later it returns OMR_ERR_INVALID_ARGUMENT and the session
+ * stays usable, without a bitmap. A second call is a no-op. A session that never enables the bitmap
+ * does exactly what it did before, and omr_digest_read_bitmap / omr_digest_merge_bitmap on it return
+ * OMR_ERR_INVALID_ARGUMENT. omr_digest_info does not describe the bitmap: its ciphertext count comes
+ * from omr_bitmap_ct_count. */
+omr_status omr_digest_enable_bitmap(omr_digest *dg);
+/* As omr_digest_read, for the bitmap: synchronises, takes a pending hand-off error (poisoning the
+ * session), then copies bitmap_cts u64 [n_ct][2][2048] to the host. */
+omr_status omr_digest_read_bitmap(omr_digest *dg, uint64_t *bitmap_cts);
+/* As omr_digest_merge, for the bitmap: adds another session's omr_digest_read_bitmap output mod q2;
+ * OMR_ERR_INVALID_ARGUMENT for a value >= q2, the bitmap unchanged. */
+omr_status omr_digest_merge_bitmap(omr_digest *dg, const uint64_t *bitmap_cts);
 /* Synchronises the session's stream and frees its buffers; NULL is ignored. */
 void omr_digest_destroy(omr_digest *dg);
 

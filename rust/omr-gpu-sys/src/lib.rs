@@ -237,6 +237,21 @@ pub mod ffi {
         pub fn omr_digest_read(dg: *mut OmrDigest, idx_cts: *mut u64, pay_cts: *mut u64) -> OmrStatus;
         pub fn omr_digest_get_info(dg: *mut OmrDigest, info: *mut OmrDigestInfo) -> OmrStatus;
         pub fn omr_digest_destroy(dg: *mut OmrDigest);
+        pub fn omr_digest_enable_bitmap(dg: *mut OmrDigest) -> OmrStatus;
+        pub fn omr_digest_read_bitmap(dg: *mut OmrDigest, bitmap_cts: *mut u64) -> OmrStatus;
+        pub fn omr_digest_merge_bitmap(dg: *mut OmrDigest, bitmap_cts: *const u64) -> OmrStatus;
+
+        // bitmap digest (none in the reference)
+        pub fn omr_bitmap_ct_count(all_payloads_count: usize, n_ct: *mut u32) -> OmrStatus;
+        pub fn omr_encode_bitmap_device(ctx: *mut OmrCtx, d_pv: *const u64, d: usize, global_offset: usize,
+                                        all_payloads_count: usize, d_out: *mut u64, hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_encode_bitmap(ctx: *mut OmrCtx, pv: *const u64, d: usize, global_offset: usize,
+                                 all_payloads_count: usize, out: *mut u64) -> OmrStatus;
+        pub fn omr_bitmap_indices(decoded: *const u16, n_ct: u32, all_payloads_count: usize, indices: *mut usize,
+                                  cap: usize, found: *mut usize) -> OmrStatus;
+        pub fn omr_retrieve_bitmap(sk: *const OmrSecretKeyPack, bitmap_cts: *const u64, n_ct: u32,
+                                   all_payloads_count: usize, indices: *mut usize, cap: usize,
+                                   found: *mut usize) -> OmrStatus;
 
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
@@ -517,6 +532,32 @@ impl GpuDetector {
         Ok(NttRlwe::from_flat(&out))
     }
 
+    /// The board's bitmap digest (`omr_encode_bitmap`, none in the reference) over the messages
+    /// `global_offset..global_offset + pv.len()`: `bitmap_ct_count(all)` ciphertexts from which
+    /// `Retriever::decode_bitmap` reads every pertinent index without knowing their number. Partial
+    /// digests of shards are summed mod q2.
+    pub fn encode_bitmap(&self, pertinency_vector: &[NttRlwe], global_offset: usize,
+                         all_payloads_count: usize) -> Result<Vec<NttRlwe>, OmrError> {
+        let pv = NttRlwe::flatten(pertinency_vector);
+        let mut out = vec![0u64; bitmap_ct_count(all_payloads_count)? * 2 * OMR_N2];
+        check(unsafe {
+            omr_encode_bitmap(self.ctx, pv.as_ptr(), pertinency_vector.len(), global_offset, all_payloads_count,
+                              out.as_mut_ptr())
+        })?;
+        Ok(out.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect())
+    }
+
+    /// The same on device buffers (`omr_encode_bitmap_device`), enqueued on `hip_stream`.
+    ///
+    /// # Safety
+    /// `d_pv` must be device memory of `d` pertinency ciphertexts (16-byte aligned) and `d_out` of
+    /// `bitmap_ct_count(all)` ciphertexts, both valid until the stream has run the call.
+    pub unsafe fn encode_bitmap_device(&self, d_pv: *const u64, d: usize, global_offset: usize,
+                                       all_payloads_count: usize, d_out: *mut u64,
+                                       hip_stream: *mut c_void) -> Result<(), OmrError> {
+        check(omr_encode_bitmap_device(self.ctx, d_pv, d, global_offset, all_payloads_count, d_out, hip_stream))
+    }
+
     /// `Detector::encode_pertinent_payloads` (detector.rs:341-350) with the 32-byte seed of
     /// `StdRng::from_seed` (same weights; the retriever regenerates them, retriever.rs:215-240).
     pub fn encode_pertinent_payloads(&self, pertinency_vector: &[NttRlwe], payloads: &[Payload],
@@ -681,6 +722,28 @@ impl DigestSession<'_> {
                     payloads: pay.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect() })
     }
 
+    /// Also keep the board's bitmap digest (`omr_digest_enable_bitmap`); before the first update or
+    /// merge, a second call is a no-op.
+    pub fn enable_bitmap(&self) -> Result<(), OmrError> {
+        check(unsafe { omr_digest_enable_bitmap(self.raw) })
+    }
+
+    /// Waits for the session's work and returns the bitmap digest so far (`omr_digest_read_bitmap`).
+    pub fn read_bitmap(&self) -> Result<Vec<NttRlwe>, OmrError> {
+        let mut out = vec![0u64; bitmap_ct_count(self.info()?.all_payloads_count)? * 2 * OMR_N2];
+        check(unsafe { omr_digest_read_bitmap(self.raw, out.as_mut_ptr()) })?;
+        Ok(out.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect())
+    }
+
+    /// Adds another session's `read_bitmap` output mod q2 (`omr_digest_merge_bitmap`).
+    pub fn merge_bitmap(&self, other: &[NttRlwe]) -> Result<(), OmrError> {
+        if other.len() != bitmap_ct_count(self.info()?.all_payloads_count)? {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "bitmap of another board".into() });
+        }
+        let cts = NttRlwe::flatten(other);
+        check(unsafe { omr_digest_merge_bitmap(self.raw, cts.as_ptr()) })
+    }
+
     pub fn info(&self) -> Result<OmrDigestInfo, OmrError> {
         let mut info = OmrDigestInfo::default();
         check(unsafe { omr_digest_get_info(self.raw, &mut info) })?;
@@ -694,6 +757,37 @@ impl Drop for DigestSession<'_> {
     }
 }
 
+/// Bitmap ciphertexts of a board, `ceil(all / 16384)` (`omr_bitmap_ct_count`).
+pub fn bitmap_ct_count(all_payloads_count: usize) -> Result<usize, OmrError> {
+    let mut n = 0u32;
+    check(unsafe { omr_bitmap_ct_count(all_payloads_count, &mut n) })?;
+    Ok(n as usize)
+}
+
+/// Runs `call(indices, cap, found)`, and once more with room for `found` if `cap` was too small.
+fn collect_indices(mut call: impl FnMut(*mut usize, usize, *mut usize) -> OmrStatus) -> Result<Vec<usize>, OmrError> {
+    let mut buf = vec![0usize; 1024];
+    loop {
+        let mut found = 0usize;
+        check(call(buf.as_mut_ptr(), buf.len(), &mut found))?;
+        if found <= buf.len() {
+            buf.truncate(found);
+            return Ok(buf);
+        }
+        buf.resize(found, 0);
+    }
+}
+
+/// The global indices of the set bits of decoded bitmap ciphertexts (`omr_bitmap_indices`):
+/// `decoded` holds 2,048 values < 256 per ciphertext, e.g. `Audit::decoded`; increasing order.
+pub fn bitmap_indices(decoded: &[u16], all_payloads_count: usize) -> Result<Vec<usize>, OmrError> {
+    if decoded.len() % OMR_N2 != 0 {
+        return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "2,048 decoded values per ciphertext".into() });
+    }
+    let n_ct = (decoded.len() / OMR_N2) as u32;
+    collect_indices(|i, cap, found| unsafe { omr_bitmap_indices(decoded.as_ptr(), n_ct, all_payloads_count, i, cap, found) })
+}
+
 /// `Retriever::decode_digest` (retriever.rs:188-260) under the pack's second-level key.
 pub struct Retriever<'a> {
     pub params: RetrievalParams,
@@ -701,6 +795,14 @@ pub struct Retriever<'a> {
 }
 
 impl<'a> Retriever<'a> {
+    /// Every pertinent index of the board, increasing, from its bitmap digest (`omr_retrieve_bitmap`):
+    /// needs no pertinent count.
+    pub fn decode_bitmap(&self, bitmap_digest: &[NttRlwe]) -> Result<Vec<usize>, OmrError> {
+        let cts = NttRlwe::flatten(bitmap_digest);
+        let (sk, n_ct, all) = (self.secret.raw, bitmap_digest.len() as u32, self.params.all_payloads_count);
+        collect_indices(|i, cap, found| unsafe { omr_retrieve_bitmap(sk, cts.as_ptr(), n_ct, all, i, cap, found) })
+    }
+
     /// Sorted pertinent indices and their payloads; `seed` is the payload-weight seed.
     pub fn decode_digest(&self, indices_digest: &[NttRlwe], payloads_digest: &[NttRlwe],
                          seed: &[u8; 32]) -> Result<(Vec<usize>, Vec<Payload>), OmrError> {

@@ -201,6 +201,12 @@ omr_status encode_indices(omr_ctx *c, const uint64_t *d_pv, size_t D, size_t off
 omr_status encode_payloads(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D, size_t offset,
                            size_t all, const uint16_t *d_weights, uint32_t n_ct, uint32_t per_ct, uint64_t *d_out,
                            hipStream_t st, bool accumulate);
+// The body of omr_encode_bitmap_device after its argument checks (bitmap_kernel.hpp): d_out is the whole
+// board's [omr_bitmap_ct_count(all)][2][N2]. accumulate = false: the touched ciphertexts are the sums of
+// their partials and the others zero; accumulate = true: the touched ones are added into, the others
+// and D = 0 leave d_out alone.
+omr_status encode_bitmap(omr_ctx *c, const uint64_t *d_pv, size_t D, size_t offset, size_t all, uint64_t *d_out,
+                         hipStream_t st, bool accumulate);
 // digest = (digest + sum over `chunks` of partial [n_ct][chunks][2][N2]) mod q2 on st
 // (accumulate_partials_kernel). Needs no context.
 omr_status accumulate_partials(const uint64_t *d_partial, int chunks, uint32_t n_ct, uint64_t *d_digest,

@@ -3,7 +3,8 @@
 // detector.rs:223-453), run piece by piece inside the library. Per piece of at most the context's
 // detect batch: detect into the session's pertinency buffer, both encode kernels over it, and the
 // chunk partials added to the running digest mod q2. The digest is an exact sum mod q2 of
-// per-message terms, so any partition of the board into updates gives the same bits.
+// per-message terms, so any partition of the board into updates gives the same bits. A session whose
+// bitmap is enabled (omr_digest_enable_bitmap) folds each piece into the bitmap digest as well.
 //
 // The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
 // context's detect / encode scratch under the context mutex (ctx.hpp), like any other call.
@@ -27,7 +28,10 @@ struct omr_digest {
   DevBuf<uint16_t> weights;      // [payload_ct * cmb_count_per_cipher][all]
   DevBuf<uint64_t> digest;       // [index_ct + payload_ct][2][N2], canonical
   DevBuf<uint64_t> pv;           // pertinency ciphertexts of one piece, grown lazily
-  DevBuf<uint64_t> merge_stage;  // omr_digest_merge's upload
+  DevBuf<uint64_t> merge_stage;  // omr_digest_merge's and omr_digest_merge_bitmap's upload
+  DevBuf<uint64_t> bitmap;       // [n_bmp][2][N2], canonical; empty until omr_digest_enable_bitmap
+  uint32_t n_bmp = 0;            // omr_bitmap_ct_count(all) once the bitmap is enabled, else 0
+  bool started = false;          // an update or a merge has been accepted: too late to enable the bitmap
   DevBuf<uint16_t> s_clue_a, s_clue_b, s_payloads;  // host updates' staging, grown together
   DigestRanges ranges;
   bool poisoned = false;  // a device-side failure may have reached the digest
@@ -73,6 +77,7 @@ omr_status run_piece(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, con
     ca = dg->s_clue_a, cb = dg->s_clue_b, pay = dg->s_payloads;
   }
   OMR_TRY(detect_device(c, ca, cb, n, dg->pv, st));
+  if (dg->n_bmp) OMR_TRY(encode_bitmap(c, dg->pv, n, offset, dg->all, dg->bitmap, st, true));
   OMR_TRY(encode_indices(c, dg->pv, n, offset, dg->all, dg->index_seed, 0, dg->n_idx(), dg->digest, st, true));
   return encode_payloads(c, dg->pv, pay, n, offset, dg->all, dg->weights, dg->n_pay(), dg->rp.cmb_count_per_cipher,
                          dg->digest + (size_t)dg->n_idx() * 2 * N2, st, true);
@@ -94,6 +99,7 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
   const size_t B = std::min(D, c->batch);
   omr_status s;
   OMR_TRY(ensure_piece(dg, B, host));  // nothing enqueued yet: the session stays usable
+  dg->started = true;
   try {
     dg->ranges.insert(offset, D);
   } catch (const std::bad_alloc &) {
@@ -164,6 +170,7 @@ extern "C" omr_status omr_digest_merge(omr_digest *dg, const uint64_t *idx_cts, 
   for (size_t i = 0; pay_cts && i < np; ++i)
     if (pay_cts[i] >= Q2) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge: payload digest value >= q2");
   HIP_TRY(hipSetDevice(dg->ctx->device));
+  dg->started = true;
   if (!dg->merge_stage.fits(ni + np)) {
     HIP_TRY(hipStreamSynchronize(dg->st));
     HIP_TRY(dg->merge_stage.reserve(ni + np));
@@ -197,6 +204,64 @@ extern "C" omr_status omr_digest_read(omr_digest *dg, uint64_t *idx_cts, uint64_
   const size_t ni = (size_t)dg->n_idx() * 2 * N2, np = (size_t)dg->n_pay() * 2 * N2;
   if (idx_cts) HIP_TRY(hipMemcpy(idx_cts, dg->digest, ni * sizeof(uint64_t), hipMemcpyDeviceToHost));
   if (pay_cts) HIP_TRY(hipMemcpy(pay_cts, dg->digest + ni, np * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_enable_bitmap(omr_digest *dg) {
+  if (!dg) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_enable_bitmap: NULL session");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_enable_bitmap");
+  if (dg->n_bmp) return OMR_OK;
+  if (dg->started)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_enable_bitmap: the session already has updates or merges");
+  uint32_t n;
+  OMR_TRY(omr_bitmap_ct_count(dg->all, &n));
+  HIP_TRY(hipSetDevice(dg->ctx->device));
+  const size_t elems = (size_t)n * 2 * N2;
+  HIP_TRY(dg->bitmap.alloc(elems));
+  HIP_TRY(hipMemsetAsync(dg->bitmap, 0, elems * sizeof(uint64_t), dg->st));
+  HIP_TRY(hipStreamSynchronize(dg->st));
+  dg->n_bmp = n;
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_merge_bitmap(omr_digest *dg, const uint64_t *cts) {
+  if (!dg || !cts) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge_bitmap: NULL argument");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_merge_bitmap");
+  if (!dg->n_bmp) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge_bitmap: the bitmap is not enabled");
+  const size_t nb = (size_t)dg->n_bmp * 2 * N2;
+  for (size_t i = 0; i < nb; ++i)
+    if (cts[i] >= Q2) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_merge_bitmap: value >= q2");
+  HIP_TRY(hipSetDevice(dg->ctx->device));
+  dg->started = true;
+  if (!dg->merge_stage.fits(nb)) {
+    HIP_TRY(hipStreamSynchronize(dg->st));
+    HIP_TRY(dg->merge_stage.reserve(nb));
+  }
+  // the upload first: a failure there leaves the bitmap as it was
+  HIP_TRY(hipMemcpyAsync(dg->merge_stage, cts, nb * sizeof(uint64_t), hipMemcpyHostToDevice, dg->st));
+  omr_status s = accumulate_partials(dg->merge_stage, 1, dg->n_bmp, dg->bitmap, dg->st);
+  if (s == OMR_OK && hipStreamSynchronize(dg->st) != hipSuccess)  // the host array may be reused
+    s = set_error(OMR_ERR_DEVICE, "omr_digest_merge_bitmap: stream synchronisation failed");
+  if (s != OMR_OK) dg->poisoned = true;
+  return s;
+}
+
+extern "C" omr_status omr_digest_read_bitmap(omr_digest *dg, uint64_t *cts) {
+  if (!dg || !cts) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read_bitmap: NULL argument");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_read_bitmap");
+  if (!dg->n_bmp) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read_bitmap: the bitmap is not enabled");
+  std::lock_guard<std::mutex> cl(dg->ctx->mu);
+  HIP_TRY(hipSetDevice(dg->ctx->device));
+  HIP_TRY(hipStreamSynchronize(dg->st));
+  omr_status s;
+  if ((s = take_handoff_error(dg->ctx)) != OMR_OK) {
+    dg->poisoned = true;
+    return s;
+  }
+  HIP_TRY(hipMemcpy(cts, dg->bitmap, (size_t)dg->n_bmp * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return OMR_OK;
 }
 

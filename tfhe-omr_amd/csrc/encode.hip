@@ -1,7 +1,9 @@
 // Encode (detector.rs:223-453): the index and payload encode kernels' launches over the context's
-// partial-sum scratch, their reduction or accumulation, and the four encode entry points.
+// partial-sum scratch, their reduction or accumulation, and the four encode entry points; the bitmap
+// digest's kernel (bitmap_kernel.hpp, none in the reference) the same way, with its two entry points.
 #include <algorithm>
 
+#include "bitmap_kernel.hpp"
 #include "ctx.hpp"
 #include "encode_kernels.hpp"
 
@@ -75,6 +77,43 @@ omr_status omr::encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *
   return lease.release();
 }
 
+omr_status omr::encode_bitmap(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all, uint64_t *out,
+                              hipStream_t st, bool accumulate) {
+  uint32_t n_all;
+  OMR_TRY(omr_bitmap_ct_count(all, &n_all));
+  constexpr size_t CT = 2 * (size_t)N2;
+  if (D == 0) {
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, n_all * CT * sizeof(uint64_t), st));
+    return OMR_OK;
+  }
+  // touched ciphertexts [c0, c1] and, per touched ciphertext, its touched slices of BMP_SLICE messages:
+  // only the first and the last can have fewer than all 128
+  const size_t c0 = offset / BMP_PER_CT, c1 = (offset + D - 1) / BMP_PER_CT, touched = c1 - c0 + 1;
+  auto slices = [&](size_t ct) {
+    const size_t lo = std::max(offset, ct * (size_t)BMP_PER_CT), hi = std::min(offset + D, (ct + 1) * (size_t)BMP_PER_CT);
+    return (hi - 1) / BMP_SLICE - lo / BMP_SLICE + 1;
+  };
+  const size_t most = touched > 2 ? BMP_PER_CT / BMP_SLICE : std::max(slices(c0), slices(c1));
+  // Slices per workgroup: as many as leave about two workgroups per compute unit (each keeps 64 KiB of
+  // loads in flight; the fastest grid at every size measured), and at least what the
+  // partials knob asks for. The bits do not depend on it.
+  const size_t wgs1 = touched * most * BMP_SPLIT, want = 2 * (size_t)std::max(c->ho.num_cu, 1);
+  const size_t spw = std::max(std::max<size_t>(1, wgs1 / want), (most + c->enc_max_chunks - 1) / c->enc_max_chunks);
+  const int chunks = (int)((most + spw - 1) / spw);
+  if (touched > 65535) return set_error(OMR_ERR_INVALID_ARGUMENT, "encode_bitmap: more than 65,535 ciphertexts in one call");
+  OMR_TRY(ensure_partial(c, touched * chunks * CT));
+  ScratchLease lease;
+  OMR_TRY(lease.acquire(c, st));
+  if (!accumulate) {
+    if (c0) HIP_TRY(hipMemsetAsync(out, 0, c0 * CT * sizeof(uint64_t), st));
+    if (c1 + 1 < n_all) HIP_TRY(hipMemsetAsync(out + (c1 + 1) * CT, 0, (n_all - c1 - 1) * CT * sizeof(uint64_t), st));
+  }
+  encode_bitmap_kernel<<<dim3(chunks, (unsigned)touched, BMP_SPLIT), BMP_T, 0, st>>>(pv, D, offset, c0, (int)spw,
+                                                                                    c->tab.tb.tw2, c->scr.partial);
+  OMR_TRY(encode_finish(c, chunks, (uint32_t)touched, out + c0 * CT, st, accumulate));
+  return lease.release();
+}
+
 extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, size_t D,
                                                 size_t offset, size_t all, uint64_t seed,
                                                 uint32_t first_ct, uint32_t n_ct, uint64_t *out,
@@ -132,6 +171,33 @@ extern "C" omr_status omr_encode_payloads(omr_ctx *c, const uint64_t *pv, const 
   HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dw, weights, wn * sizeof(uint16_t), hipMemcpyHostToDevice));
   OMR_TRY(omr_encode_payloads_device(c, dpv, dpay, D, offset, all, dw, n_ct, per_ct, dout, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_encode_bitmap_device(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all,
+                                               uint64_t *out, void *stream) {
+  if (!c || !out || (D && !pv) || all == 0 || offset > all || D > all - offset || D > (size_t)INT32_MAX ||
+      ((uintptr_t)pv & 15) != 0)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_bitmap_device: bad argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // NULL: HIP's null stream
+  return encode_bitmap(c, pv, D, offset, all, out, (hipStream_t)stream, false);
+}
+
+extern "C" omr_status omr_encode_bitmap(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all,
+                                        uint64_t *out) {
+  uint32_t n_ct;
+  if (!c || !out || (D && !pv)) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_bitmap");
+  OMR_TRY(omr_bitmap_ct_count(all, &n_ct));
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<uint64_t> dpv, dout;
+  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
+  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
+  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  OMR_TRY(omr_encode_bitmap_device(c, dpv, D, offset, all, dout, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return OMR_OK;

@@ -1,6 +1,7 @@
 // Client-side digest decoding (host, CPU): Retriever::decode_digest (retriever.rs:188-260) with
 // decode_pertinent_indices (:63-130), decode_combined_payloads (:318-362) and
-// solve_matrix_mod_257 (matrix.rs:164-247). Used by clients of the detector, by bench.py's
+// solve_matrix_mod_257 (matrix.rs:164-247), and the bitmap digest's decoding (include/omr_gpu.h, "Bitmap
+// digest": none in the reference). Used by clients of the detector, by bench.py's
 // end-to-end check and by the multi-GPU driver; needs only the secret key pack.
 #include <mutex>
 #include <set>
@@ -192,4 +193,54 @@ extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const
   for (size_t k = 0; k < cols; ++k)
     for (int b = 0; b < PAYLOAD_LEN; ++b) payloads[k * PAYLOAD_LEN + b] = (uint16_t)rhs[k][b];
   return OMR_OK;
+}
+
+extern "C" omr_status omr_bitmap_ct_count(size_t all, uint32_t *n_ct) {
+  if (!n_ct) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_bitmap_ct_count: NULL argument");
+  const size_t n = all / OMR_BITMAP_MESSAGES_PER_CT + (all % OMR_BITMAP_MESSAGES_PER_CT != 0);
+  if (all == 0 || n > UINT32_MAX) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_bitmap_ct_count: bad board size");
+  *n_ct = (uint32_t)n;
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_bitmap_indices(const uint16_t *decoded, uint32_t n_ct, size_t all, size_t *indices,
+                                         size_t cap, size_t *found) {
+  if (!decoded || !found || (cap && !indices))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_bitmap_indices: NULL argument");
+  uint32_t want;
+  const omr_status st = omr_bitmap_ct_count(all, &want);
+  if (st != OMR_OK) return st;
+  const char *bad = "omr_bitmap_indices: not a bitmap digest of this board";
+  if (n_ct != want) return set_error(OMR_ERR_INVALID_ARGUMENT, bad);
+  size_t n = 0;
+  // increasing g = 16384 c + 2048 t + j: ciphertext, then bit plane, then coefficient
+  for (uint32_t c = 0; c < n_ct; ++c) {
+    const uint16_t *d = decoded + (size_t)c * N2;
+    for (int j = 0; j < N2; ++j)
+      if (d[j] >> OMR_BITMAP_BITS) return set_error(OMR_ERR_INVALID_ARGUMENT, bad);
+    for (int t = 0; t < OMR_BITMAP_BITS; ++t)
+      for (int j = 0; j < N2; ++j) {
+        if (!((d[j] >> t) & 1)) continue;
+        const size_t g = (size_t)c * OMR_BITMAP_MESSAGES_PER_CT + (size_t)t * N2 + j;
+        if (g >= all) return set_error(OMR_ERR_INVALID_ARGUMENT, bad);
+        if (n < cap) indices[n] = g;
+        ++n;
+      }
+  }
+  *found = n;
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_retrieve_bitmap(const omr_secret_key_pack *sk, const uint64_t *bitmap_cts, uint32_t n_ct,
+                                          size_t all, size_t *indices, size_t cap, size_t *found) {
+  if (!sk || !bitmap_cts || !found || (cap && !indices))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_bitmap: NULL argument");
+  uint32_t want;
+  const omr_status st = omr_bitmap_ct_count(all, &want);
+  if (st != OMR_OK) return st;
+  if (n_ct != want) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_bitmap: not a bitmap digest of this board");
+  std::vector<uint32_t> dec((size_t)n_ct * N2);
+  parallel_for(n_ct, 0, [&](size_t c) { decrypt_decode_one(sk, bitmap_cts + c * 2 * N2, P, &dec[c * N2]); });
+  const std::vector<uint16_t> d16(dec.begin(), dec.end());  // decoded values are < 257
+  return omr_bitmap_indices(d16.data(), n_ct, all, indices, cap, found);
 }

@@ -4,13 +4,17 @@
 // encode_pertinent_payloads, client-side retrieval, and a check that exactly the pertinent
 // indices and their payloads come back.
 //
-//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--host-only]
+//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
 // --audit checks the detector's output on the GPU with the recipient's secret (omr_audit): every pertinent
 // message's ciphertext must decrypt to [1, 0, .., 0], every other one to zeros (with --session there is
 // no pertinency vector to audit), and the digests' decode residuals are reported.
+// --bitmap takes the pertinent indices from the bitmap digest (omr_encode_bitmap, or the session's with
+// omr_digest_enable_bitmap; omr_retrieve_bitmap), which needs no pertinent count, instead of the index
+// digest; the payloads are then solved for those indices. With --host-only it checks the bitmap's layout
+// on the host (omr_bitmap_ct_count, omr_bitmap_indices on the board's own pertinent set).
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -51,7 +55,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false;
+  bool audit = false, bitmap = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if ((a == "-p" || a == "--payload-count") && i + 1 < argc) D = std::max<size_t>(1, std::stoull(argv[++i]));
@@ -59,9 +63,10 @@ int main(int argc, char **argv) {
     else if ((a == "-s" || a == "--seed") && i + 1 < argc) seed = std::stoull(argv[++i]);
     else if (a == "--session" && i + 1 < argc) session_piece = std::max<size_t>(1, std::stoull(argv[++i]));
     else if (a == "--audit") audit = true;
+    else if (a == "--bitmap") bitmap = true;
     else if (a == "--host-only") host_only = true;
     else {
-      std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] "
+      std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
                    "[--host-only]\n",
                    argv[0]);
       return 2;
@@ -115,6 +120,24 @@ int main(int argc, char **argv) {
                             weights.data()));
   std::printf("retrieval params: %u index ct, %u payload ct (%u combinations)\n",
               rp.max_encode_indices_cipher_count, rp.cmb_cipher_count, rp.combination_count);
+  uint32_t n_bmp = 0;
+  if (bitmap) CHECK(omr_bitmap_ct_count(D, &n_bmp));
+  if (host_only && bitmap) {
+    // the layout on the host: the board's pertinent set as decoded bitmap values, and back
+    std::vector<uint16_t> dec((size_t)n_bmp * N2, 0);
+    for (size_t g : pert) {
+      const size_t l = g % OMR_BITMAP_MESSAGES_PER_CT;
+      dec[g / OMR_BITMAP_MESSAGES_PER_CT * N2 + l % N2] |= (uint16_t)(1u << (l / N2));
+    }
+    std::vector<size_t> back(pert_count);
+    size_t nback = 0;
+    CHECK(omr_bitmap_indices(dec.data(), n_bmp, D, back.data(), back.size(), &nback));
+    if (nback != pert_count || back != pert) {
+      std::printf("Fail: bitmap layout returns %zu indices, %zu pertinent\nFAILED\n", nback, pert.size());
+      return 1;
+    }
+    std::printf("host-only: bitmap layout OK (%u bitmap ct, %zu indices)\n", n_bmp, nback);
+  }
   if (host_only) {
     std::printf("host-only: keys, clues, weights and parameters OK\n");
     omr_secret_destroy(pa);
@@ -131,17 +154,19 @@ int main(int argc, char **argv) {
   if (audit) CHECK(omr_auditor_create(pa, device, &aud));
   int audit_fails = 0;
   omr_audit_summary pv_sum{}, dg_sum{};
-  std::vector<uint64_t> idx_ct((size_t)n_idx * 2 * N2), pay_ct((size_t)n_pay * 2 * N2);
+  std::vector<uint64_t> idx_ct((size_t)n_idx * 2 * N2), pay_ct((size_t)n_pay * 2 * N2), bmp_ct((size_t)n_bmp * 2 * N2);
   if (session_piece) {
     // the same flow inside the library, piece by piece (omr_digest_*): detect + both encoders
     t = clk::now();
     omr_digest *dg = nullptr;
     CHECK(omr_digest_begin(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
+    if (bitmap) CHECK(omr_digest_enable_bitmap(dg));
     for (size_t off = 0; off < D; off += session_piece) {
       const size_t n = std::min(session_piece, D - off);
       CHECK(omr_digest_update(dg, &ca[off * N0], &cb[off * CLUES], &payloads[off * PAYLOAD], n, off));
     }
     CHECK(omr_digest_read(dg, idx_ct.data(), pay_ct.data()));
+    if (bitmap) CHECK(omr_digest_read_bitmap(dg, bmp_ct.data()));
     omr_digest_info info;
     CHECK(omr_digest_get_info(dg, &info));
     omr_digest_destroy(dg);
@@ -183,6 +208,11 @@ int main(int argc, char **argv) {
     CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
                               rp.cmb_count_per_cipher, pay_ct.data()));
     std::printf("encode pertinent payloads time: %.3f s\n", secs(t));
+    if (bitmap) {
+      t = clk::now();
+      CHECK(omr_encode_bitmap(ctx, pv.data(), D, 0, D, bmp_ct.data()));
+      std::printf("encode bitmap time: %.3f s\n", secs(t));
+    }
   }
 
   if (audit) {
@@ -193,6 +223,12 @@ int main(int argc, char **argv) {
                 (unsigned long long)pv_sum.one_hot, (unsigned long long)pv_sum.zero, (unsigned long long)pv_sum.other,
                 (double)pv_sum.max_abs_residual / (double)OMR_Q2, (unsigned long long)dg_sum.ciphertexts,
                 (double)dg_sum.max_abs_residual / (double)OMR_Q2, audit_fails ? " -- FAILED" : "");
+    if (bitmap) {
+      omr_audit_summary bmp_sum{};
+      CHECK(omr_audit(aud, bmp_ct.data(), n_bmp, nullptr, nullptr, &bmp_sum));
+      std::printf("audit: bitmap digest %u ciphertexts, max |r|/q2 %.3e (decode limit 0.5)\n", n_bmp,
+                  (double)bmp_sum.max_abs_residual / (double)OMR_Q2);
+    }
     omr_auditor_destroy(aud);
   }
 
@@ -200,7 +236,14 @@ int main(int argc, char **argv) {
   t = clk::now();
   std::vector<size_t> found(pert_count + 64);
   size_t nfound = 0;
-  CHECK(omr_retrieve_indices(pa, idx_ct.data(), n_idx, D, pert_count, found.data(), found.size(), &nfound));
+  if (bitmap) {
+    // no count needed: the bitmap says how many there are, and whether the board's layout covers them
+    CHECK(omr_retrieve_bitmap(pa, bmp_ct.data(), n_bmp, D, found.data(), found.size(), &nfound));
+    std::printf("bitmap digest: %u ciphertexts, %zu pertinent indices (the board's %u combinations %s)\n", n_bmp,
+                nfound, rp.combination_count, nfound <= rp.combination_count ? "cover them" : "do NOT cover them");
+  } else {
+    CHECK(omr_retrieve_indices(pa, idx_ct.data(), n_idx, D, pert_count, found.data(), found.size(), &nfound));
+  }
   found.resize(std::min(nfound, found.size()));
   std::vector<uint16_t> solved(found.size() * PAYLOAD);
   CHECK(omr_retrieve_payloads(pa, pay_ct.data(), n_pay, D, rp.combination_count, weights.data(), found.data(), found.size(),

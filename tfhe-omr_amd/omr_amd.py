@@ -117,6 +117,16 @@ EXPORTS = {
     "omr_encode_payloads_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                              C.c_void_p]),
+    "omr_bitmap_ct_count": (C.c_int, [C.c_size_t, C.POINTER(C.c_uint32)]),
+    "omr_encode_bitmap": (C.c_int, [C.c_void_p, _u64p, C.c_size_t, C.c_size_t, C.c_size_t, _u64p]),
+    "omr_encode_bitmap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                           C.c_void_p]),
+    "omr_bitmap_indices": (C.c_int, [_u16p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "omr_retrieve_bitmap": (C.c_int, [C.c_void_p, _u64p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "omr_digest_enable_bitmap": (C.c_int, [C.c_void_p]),
+    "omr_digest_read_bitmap": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "omr_digest_merge_bitmap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "omr_digest_begin": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),
     "omr_digest_update": (C.c_int, [C.c_void_p, _u16p, _u16p, _u16p, C.c_size_t, C.c_size_t]),
@@ -355,6 +365,39 @@ def fft_twiddles_dd(level: int) -> np.ndarray:
     return out.reshape(n - 1, 4)
 
 
+BITMAP_BITS, BITMAP_MESSAGES_PER_CT = 8, 16384
+
+
+def bitmap_ct_count(all_payloads_count: int) -> int:
+    """omr_bitmap_ct_count: bitmap ciphertexts of a board, ceil(all / 16384)."""
+    n = C.c_uint32()
+    _check(lib().omr_bitmap_ct_count(all_payloads_count, C.byref(n)), "omr_bitmap_ct_count")
+    return n.value
+
+
+def _indices_call(call, what, cap):
+    """Runs call(indices pointer, cap, found) and once more with room for `found` if cap was too small."""
+    while True:
+        buf = np.zeros(max(1, cap), dtype=np.uintp)
+        found = C.c_size_t()
+        _check(call(buf.ctypes.data, buf.size, C.byref(found)), what)
+        if found.value <= buf.size:
+            return [int(v) for v in buf[:found.value]]
+        cap = found.value
+
+
+def bitmap_indices(decoded, all_payloads_count: int, cap: int = 1024) -> list[int]:
+    """omr_bitmap_indices: the global indices of the set bits of decoded bitmap ciphertexts
+    ([n_ct][2048] values < 256, e.g. Auditor.audit's `decoded` or Retriever.decrypt_decode), increasing."""
+    d = np.ascontiguousarray(decoded).reshape(-1, N2)
+    if d.dtype != np.uint16:
+        if (d > 0xFFFF).any():
+            raise OmrError("decoded bitmap values must fit 16 bits")
+        d = d.astype(np.uint16)
+    return _indices_call(lambda i, c, f: lib().omr_bitmap_indices(d.reshape(-1), d.shape[0], all_payloads_count,
+                                                                  i, c, f), "omr_bitmap_indices", cap)
+
+
 def detect_kernels() -> dict:
     """{'br1': name, 'ks': name, 'br2': name} of the kernels this build launches."""
     return dict(kv.split("=") for kv in lib().omr_detect_kernels().decode().split())
@@ -395,6 +438,14 @@ class Retriever:
                                            np.ascontiguousarray(weights, dtype=np.uint16).reshape(-1), idx,
                                            len(idx), out.reshape(-1)), "omr_retrieve_payloads")
         return out
+
+    def decode_bitmap(self, bitmap_cts, cap: int = 1024) -> list[int]:
+        """omr_retrieve_bitmap: every pertinent global index of the board, increasing, from its bitmap
+        digest u64 [bitmap_ct_count(all)][2][2048]; needs no pertinent count."""
+        cts = np.ascontiguousarray(bitmap_cts, dtype=np.uint64).reshape(-1, 2, N2)
+        return _indices_call(lambda i, c, f: lib().omr_retrieve_bitmap(
+            self._sk._h, cts.reshape(-1), cts.shape[0], self.params.all_payloads_count, i, c, f),
+            "omr_retrieve_bitmap", cap)
 
     def decode_digest(self, idx_cts, pay_cts, seed: bytes):
         """Retriever::decode_digest: sorted pertinent indices and their payloads (mod 257); the
@@ -682,7 +733,21 @@ class Detector:
                                          rp.all_payloads_count, w, n_ct, per, out.reshape(-1)), "omr_encode_payloads")
         return out
 
+    def encode_bitmap(self, pertinency_vector, all_payloads_count: int, global_offset: int = 0) -> np.ndarray:
+        """omr_encode_bitmap (none in the reference): the board's bitmap digest u64
+        [bitmap_ct_count(all)][2][2048] over the messages global_offset.. of the pertinency vector."""
+        pv = np.ascontiguousarray(pertinency_vector, dtype=np.uint64).reshape(-1, 2, N2)
+        out = np.empty((bitmap_ct_count(all_payloads_count), 2, N2), np.uint64)
+        _check(lib().omr_encode_bitmap(self._h, pv.reshape(-1), pv.shape[0], global_offset, all_payloads_count,
+                                       out.reshape(-1)), "omr_encode_bitmap")
+        return out
+
     # device-pointer variants (chaining on the caller's HIP stream; pointers are raw addresses)
+    def encode_bitmap_device(self, d_pv: int, D: int, global_offset: int, all_payloads_count: int, d_out: int,
+                             stream: int = 0) -> None:
+        _check(lib().omr_encode_bitmap_device(self._h, d_pv or None, D, global_offset, all_payloads_count, d_out,
+                                              stream or None), "omr_encode_bitmap_device")
+
     def encode_indices_device(self, d_pv: int, D: int, global_offset: int, all_payloads_count: int, seed: int,
                               first_ct: int, n_ct: int, d_out: int, stream: int = 0) -> None:
         _check(lib().omr_encode_indices_device(self._h, d_pv, D, global_offset, all_payloads_count, seed, first_ct,
@@ -796,6 +861,23 @@ class DigestSession:
         pay = np.empty((self._info["payload_ct"], 2, N2), np.uint64)
         _check(lib().omr_digest_read(self._h, idx.ctypes.data, pay.ctypes.data), "omr_digest_read")
         return idx, pay
+
+    def enable_bitmap(self) -> None:
+        """omr_digest_enable_bitmap: also keep the board's bitmap digest; before the first update or merge."""
+        _check(lib().omr_digest_enable_bitmap(self._h), "omr_digest_enable_bitmap")
+
+    def read_bitmap(self) -> np.ndarray:
+        """The bitmap digest u64 [bitmap_ct_count(all)][2][2048] after a stream sync."""
+        out = np.empty((bitmap_ct_count(self._info["all_payloads_count"]), 2, N2), np.uint64)
+        _check(lib().omr_digest_read_bitmap(self._h, out.ctypes.data), "omr_digest_read_bitmap")
+        return out
+
+    def merge_bitmap(self, bitmap_cts) -> None:
+        """Add another session's read_bitmap() output mod q2."""
+        b = np.ascontiguousarray(bitmap_cts, dtype=np.uint64)
+        if b.size != bitmap_ct_count(self._info["all_payloads_count"]) * 2 * N2:
+            raise OmrError("bitmap array must be u64 [bitmap_ct_count(all)][2][2048]")
+        _check(lib().omr_digest_merge_bitmap(self._h, b.ctypes.data), "omr_digest_merge_bitmap")
 
     def info(self) -> dict:
         t = _DigestInfo()
