@@ -96,6 +96,76 @@ omr_status omr_keygen_detection_key_device(const omr_secret_key_pack *sk, uint64
                                            uint64_t *d_trace_key, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Seeded detection key (none in the reference): the form a recipient sends and a server stores.
+ * More than half of a detection key is uniform masks that carry no secret (the `a` half of every
+ * RLWE row, 670 of the 671 words of every key-switching row). A seeded key carries a public 64-bit
+ * mask_seed instead and only the bodies:
+ *      bsk1_b      u32 [512][8][1024]    16,777,216 B
+ *      ksk_b       u32 [1024][27]           110,592 B
+ *      bsk2_b      u64 [670][12][2048]  131,727,360 B
+ *      trace_key_b u64 [11][25][2048]     4,505,600 B
+ *      mask_seed   u64                            8 B    153,120,776 B against 380,227,584 B
+ *
+ * Definition. Stream(seed, domain, row) is the ChaCha12 row stream of the generators above (key
+ * words seed lo, seed hi, "keyg", domain, 0, 0, 0, 0; block counter from 0; stream id = the row of the
+ * component); uniform(q) takes 64 bits, keeps the bit length of q and rejects values >= q.
+ *  - The mask of row r of a component is the first N accepted draws of
+ *    Stream(mask_seed, DOM_*_MASK, r).uniform(q), N = 1024 / 670 / 2048 / 2048; mask domains
+ *    30 (bsk1), 31 (ksk), 32 (bsk2), 33 (trace_key).
+ *  - The noise of row r is Gaussian draws (the generators' tables) from Stream(seed, DOM_*_NOISE, r),
+ *    starting at the stream's first word; noise domains 40, 41, 42, 43. They are domains of their own
+ *    on purpose: omr_keygen_detection_key(seed) draws a row's mask and then its noise from one stream
+ *    and publishes the mask, so a seeded key whose noise came from that stream's first words would
+ *    have its noise published by a plain key generated from the same seed.
+ *  - Rows, with mg, the component of the gadget, sigma_g and the gadget values exactly those of
+ *    omr_keygen_detection_key, products in Z_q[X]/(X^N+1):
+ *      BSK a-gadget row:  a = mask, b = a*s + e - mg*s      (s ternary, mg*s coefficient-wise)
+ *      BSK b-gadget row:  a = mask, b = a*s + e, plus mg at coefficient 0
+ *      trace-key row:     a = mask, b = a*s2 + e - sigma_g(s2) * 4^j
+ *      KSK row:           a[670] = mask, b = <a, s_int> + e + s1_i * 2^j
+ *    The a-gadget row is the layout's (alpha + m g, alpha s + e) with alpha = a - mg: same phase
+ *    e - mg*s, same distribution. The expanded key is therefore an ordinary detection key for every
+ *    entry point below, and its `a` words are a function of the public seed alone. It is a new key:
+ *    it does not equal omr_keygen_detection_key(seed), whose output is unchanged.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  const uint32_t *bsk1_b;
+  const uint32_t *ksk_b;
+  const uint64_t *bsk2_b;
+  const uint64_t *trace_key_b;
+  uint64_t mask_seed;
+} omr_seeded_key_view;
+
+typedef enum { OMR_KEY_BSK1 = 0, OMR_KEY_KSK = 1, OMR_KEY_BSK2 = 2, OMR_KEY_TRACE = 3 } omr_key_component;
+
+/* The bodies of the seeded key of (sk, seed, mask_seed), on the host; nthreads <= 0: all host cores. */
+omr_status omr_keygen_seeded_key(const omr_secret_key_pack *sk, uint64_t seed, uint64_t mask_seed,
+                                 uint32_t *bsk1_b, uint32_t *ksk_b, uint64_t *bsk2_b,
+                                 uint64_t *trace_key_b, int nthreads);
+/* The same bits into device buffers of the current HIP device on `stream`; returns after the stream has
+ * completed the work. */
+omr_status omr_keygen_seeded_key_device(const omr_secret_key_pack *sk, uint64_t seed, uint64_t mask_seed,
+                                        uint32_t *d_bsk1_b, uint32_t *d_ksk_b, uint64_t *d_bsk2_b,
+                                        uint64_t *d_trace_key_b, void *stream);
+/* Seeded key -> the full key in the coefficient-domain layout (host buffers). */
+omr_status omr_expand_detection_key(const omr_seeded_key_view *key, uint32_t *bsk1, uint32_t *ksk,
+                                    uint64_t *bsk2, uint64_t *trace_key, int nthreads);
+/* The same bits into device buffers of the current HIP device (16-byte aligned) on `stream`. Each body
+ * may lie in host memory or in device memory of that device (16-byte aligned); a host body is staged
+ * through a device buffer of at most 64 MiB. Returns after the stream has completed the work;
+ * OMR_ERR_DEVICE ("uniform stream overrun") if a mask row rejects more than 32 draws. */
+omr_status omr_expand_detection_key_device(const omr_seeded_key_view *key, uint32_t *d_bsk1, uint32_t *d_ksk,
+                                           uint64_t *d_bsk2, uint64_t *d_trace_key, void *stream);
+/* Stage entry points (tests): the masks of rows [first_row, first_row + rows) of one component and
+ * nothing else, out [rows][N], u32 for OMR_KEY_BSK1 and OMR_KEY_KSK (N = 1024, 670), u64 for
+ * OMR_KEY_BSK2 and OMR_KEY_TRACE (N = 2048). OMR_ERR_INVALID_ARGUMENT for a component that does not
+ * exist or a range beyond the component (4096, 27648, 8040, 275 rows). The device call writes a
+ * device buffer (16-byte aligned) on `stream` and returns after the stream has completed the work. */
+omr_status omr_key_masks(uint64_t mask_seed, int component, size_t first_row, size_t rows, void *out);
+omr_status omr_key_masks_device(uint64_t mask_seed, int component, size_t first_row, size_t rows,
+                                void *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Retrieval layout — RetrievalParams::new(257, 2048, all, pertinent, 130, 25, 2)
  * (parameters/retrieval_params.rs:50-106; arguments as in key_gen/secret.rs:189-209).
  * ------------------------------------------------------------------------------------- */
@@ -214,6 +284,11 @@ typedef struct {
 } omr_detection_key_view;
 
 omr_status omr_ctx_create(const omr_detection_key_view *key, int device, omr_ctx **out);
+/* The same context from a seeded key (bodies in host memory or in device memory of `device`): expands
+ * it on the device (omr_expand_detection_key_device) into temporary buffers, runs exactly the creation
+ * path of omr_ctx_create on them and frees them before it returns. The temporaries are the full key,
+ * 380,227,584 B (362.6 MiB), plus at most 64 MiB of staging while a host body is expanded. */
+omr_status omr_ctx_create_seeded(const omr_seeded_key_view *key, int device, omr_ctx **out);
 void omr_ctx_destroy(omr_ctx *ctx);
 /* Kernel names of this build's detect pipeline: "br1=<name> ks=<name> br2=<name>". */
 const char *omr_detect_kernels(void);

@@ -125,6 +125,21 @@ pub mod ffi {
         pub bsk2: *const u64,
         pub trace_key: *const u64,
     }
+    /// The seeded form of a detection key: the bodies and the public mask seed.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct OmrSeededKeyView {
+        pub bsk1_b: *const u32,
+        pub ksk_b: *const u32,
+        pub bsk2_b: *const u64,
+        pub trace_key_b: *const u64,
+        pub mask_seed: u64,
+    }
+    /// `omr_key_component`: the `component` argument of `omr_key_masks`.
+    pub const OMR_KEY_BSK1: c_int = 0;
+    pub const OMR_KEY_KSK: c_int = 1;
+    pub const OMR_KEY_BSK2: c_int = 2;
+    pub const OMR_KEY_TRACE: c_int = 3;
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
     pub struct OmrDetectTiming {
@@ -155,6 +170,23 @@ pub mod ffi {
         pub fn omr_keygen_detection_key_device(sk: *const OmrSecretKeyPack, seed: u64, d_bsk1: *mut u32,
                                                d_ksk: *mut u32, d_bsk2: *mut u64, d_trace_key: *mut u64,
                                                stream: *mut c_void) -> OmrStatus;
+
+        // seeded detection key: the bodies of a key whose masks come from a public seed
+        pub fn omr_keygen_seeded_key(sk: *const OmrSecretKeyPack, seed: u64, mask_seed: u64, bsk1_b: *mut u32,
+                                     ksk_b: *mut u32, bsk2_b: *mut u64, trace_key_b: *mut u64,
+                                     nthreads: c_int) -> OmrStatus;
+        pub fn omr_keygen_seeded_key_device(sk: *const OmrSecretKeyPack, seed: u64, mask_seed: u64,
+                                            d_bsk1_b: *mut u32, d_ksk_b: *mut u32, d_bsk2_b: *mut u64,
+                                            d_trace_key_b: *mut u64, stream: *mut c_void) -> OmrStatus;
+        pub fn omr_expand_detection_key(key: *const OmrSeededKeyView, bsk1: *mut u32, ksk: *mut u32,
+                                        bsk2: *mut u64, trace_key: *mut u64, nthreads: c_int) -> OmrStatus;
+        pub fn omr_expand_detection_key_device(key: *const OmrSeededKeyView, d_bsk1: *mut u32, d_ksk: *mut u32,
+                                               d_bsk2: *mut u64, d_trace_key: *mut u64,
+                                               stream: *mut c_void) -> OmrStatus;
+        pub fn omr_key_masks(mask_seed: u64, component: c_int, first_row: usize, rows: usize,
+                             out: *mut c_void) -> OmrStatus;
+        pub fn omr_key_masks_device(mask_seed: u64, component: c_int, first_row: usize, rows: usize,
+                                    d_out: *mut c_void, stream: *mut c_void) -> OmrStatus;
 
         // retrieval layout and payload weights (retrieval_params.rs:50-106, detector.rs:376-387)
         pub fn omr_get_retrieval_params(all_payloads_count: usize, pertinent_count: usize,
@@ -187,6 +219,7 @@ pub mod ffi {
 
         // detector (detector.rs:85-453)
         pub fn omr_ctx_create(key: *const OmrDetectionKeyView, device: c_int, out: *mut *mut OmrCtx) -> OmrStatus;
+        pub fn omr_ctx_create_seeded(key: *const OmrSeededKeyView, device: c_int, out: *mut *mut OmrCtx) -> OmrStatus;
         pub fn omr_ctx_destroy(ctx: *mut OmrCtx);
         pub fn omr_detect_kernels() -> *const c_char;
         pub fn omr_ctx_set_batch(ctx: *mut OmrCtx, batch: usize) -> OmrStatus;
@@ -375,6 +408,44 @@ pub const KSK_LEN: usize = OMR_N1 * OMR_KS_DIGITS * (OMR_NI + 1);
 pub const BSK2_LEN: usize = OMR_NI * 12 * 2 * OMR_N2;
 pub const TRACE_KEY_LEN: usize = OMR_TRACE_STEPS * OMR_TRACE_DIGITS * 2 * OMR_N2;
 
+/// The seeded form of a `DetectionKey` (include/omr_gpu.h): the bodies and the public mask seed,
+/// 153,120,776 bytes instead of 380,227,584.
+pub struct SeededKey {
+    pub bsk1_b: Vec<u32>,
+    pub ksk_b: Vec<u32>,
+    pub bsk2_b: Vec<u64>,
+    pub trace_key_b: Vec<u64>,
+    pub mask_seed: u64,
+}
+
+pub const BSK1_B_LEN: usize = BSK1_LEN / 2;
+pub const KSK_B_LEN: usize = OMR_N1 * OMR_KS_DIGITS;
+pub const BSK2_B_LEN: usize = BSK2_LEN / 2;
+pub const TRACE_KEY_B_LEN: usize = TRACE_KEY_LEN / 2;
+
+impl SeededKey {
+    fn view(&self) -> Result<OmrSeededKeyView, OmrError> {
+        if self.bsk1_b.len() != BSK1_B_LEN || self.ksk_b.len() != KSK_B_LEN || self.bsk2_b.len() != BSK2_B_LEN
+            || self.trace_key_b.len() != TRACE_KEY_B_LEN
+        {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "seeded key sizes".into() });
+        }
+        Ok(OmrSeededKeyView { bsk1_b: self.bsk1_b.as_ptr(), ksk_b: self.ksk_b.as_ptr(), bsk2_b: self.bsk2_b.as_ptr(),
+                              trace_key_b: self.trace_key_b.as_ptr(), mask_seed: self.mask_seed })
+    }
+    /// `omr_expand_detection_key`: the full key on `nthreads` host threads (0: all).
+    pub fn expand(&self, nthreads: i32) -> Result<DetectionKey, OmrError> {
+        let view = self.view()?;
+        let mut k = DetectionKey { bsk1: vec![0; BSK1_LEN], ksk: vec![0; KSK_LEN], bsk2: vec![0; BSK2_LEN],
+                                   trace_key: vec![0; TRACE_KEY_LEN] };
+        check(unsafe {
+            omr_expand_detection_key(&view, k.bsk1.as_mut_ptr(), k.ksk.as_mut_ptr(), k.bsk2.as_mut_ptr(),
+                                     k.trace_key.as_mut_ptr(), nthreads)
+        })?;
+        Ok(k)
+    }
+}
+
 /// `SecretKeyPack` from `KeyGen::generate_secret_key`, deterministic from a 64-bit seed.
 pub struct SecretKeyPack {
     raw: *mut OmrSecretKeyPack,
@@ -395,6 +466,16 @@ impl SecretKeyPack {
         check(unsafe {
             omr_keygen_detection_key(self.raw, seed, k.bsk1.as_mut_ptr(), k.ksk.as_mut_ptr(), k.bsk2.as_mut_ptr(),
                                      k.trace_key.as_mut_ptr(), nthreads)
+        })?;
+        Ok(k)
+    }
+    /// `omr_keygen_seeded_key`: the bodies of the key whose masks come from the public `mask_seed`.
+    pub fn generate_seeded_key(&self, seed: u64, mask_seed: u64, nthreads: i32) -> Result<SeededKey, OmrError> {
+        let mut k = SeededKey { bsk1_b: vec![0; BSK1_B_LEN], ksk_b: vec![0; KSK_B_LEN], bsk2_b: vec![0; BSK2_B_LEN],
+                                trace_key_b: vec![0; TRACE_KEY_B_LEN], mask_seed };
+        check(unsafe {
+            omr_keygen_seeded_key(self.raw, seed, mask_seed, k.bsk1_b.as_mut_ptr(), k.ksk_b.as_mut_ptr(),
+                                  k.bsk2_b.as_mut_ptr(), k.trace_key_b.as_mut_ptr(), nthreads)
         })?;
         Ok(k)
     }
@@ -464,6 +545,15 @@ impl GpuDetector {
                                          trace_key: key.trace_key.as_ptr() };
         let mut ctx = std::ptr::null_mut();
         check(unsafe { omr_ctx_create(&view, device, &mut ctx) })?;
+        Ok(Self { ctx })
+    }
+
+    /// The same detector from a seeded key (`omr_ctx_create_seeded`): the key is expanded on `device`
+    /// and the expanded copy freed before this returns.
+    pub fn from_seeded_key(key: &SeededKey, device: i32) -> Result<Self, OmrError> {
+        let view = key.view()?;
+        let mut ctx = std::ptr::null_mut();
+        check(unsafe { omr_ctx_create_seeded(&view, device, &mut ctx) })?;
         Ok(Self { ctx })
     }
 

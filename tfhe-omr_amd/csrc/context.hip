@@ -212,16 +212,18 @@ omr_status create_bounds(omr_ctx *c) {
   return x.guard_auto[0] ? ensure_bsk1n(c) : OMR_OK;  // the re-run target of a guarded level 1
 }
 
-}  // namespace
-
-extern "C" omr_status omr_ctx_create(const omr_detection_key_view *key, int device, omr_ctx **out) {
-  if (!key || !out || !key->bsk1 || !key->ksk || !key->bsk2 || !key->trace_key)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_ctx_create: NULL key component");
+omr_status select_device(int device, const char *who) {
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_ctx_create: no such device");
+    return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": no such device");
   HIP_TRY(hipSetDevice(device));
+  return OMR_OK;
+}
+
+// The creation path of both entry points: a context on the current device (`device`) from a full key
+// in host or device memory.
+omr_status create_ctx(const omr_detection_key_view *key, int device, omr_ctx **out) {
   // every early return destroys the half-built context (synchronised first, as omr_ctx_destroy does)
   std::unique_ptr<omr_ctx, decltype(&omr_ctx_destroy)> c(new omr_ctx(), &omr_ctx_destroy);
   c->device = device;
@@ -250,6 +252,31 @@ extern "C" omr_status omr_ctx_create(const omr_detection_key_view *key, int devi
   OMR_TRY(ensure_batch(c.get(), c->batch));
   *out = c.release();
   return OMR_OK;
+}
+
+}  // namespace
+
+extern "C" omr_status omr_ctx_create(const omr_detection_key_view *key, int device, omr_ctx **out) {
+  if (!key || !out || !key->bsk1 || !key->ksk || !key->bsk2 || !key->trace_key)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_ctx_create: NULL key component");
+  OMR_TRY(select_device(device, "omr_ctx_create"));
+  return create_ctx(key, device, out);
+}
+
+extern "C" omr_status omr_ctx_create_seeded(const omr_seeded_key_view *key, int device, omr_ctx **out) {
+  if (!key || !out || !key->bsk1_b || !key->ksk_b || !key->bsk2_b || !key->trace_key_b)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_ctx_create_seeded: NULL key component");
+  OMR_TRY(select_device(device, "omr_ctx_create_seeded"));
+  // the expanded key lives until the context holds its own converted copy
+  DevBuf<uint32_t> bsk1, ksk;
+  DevBuf<uint64_t> bsk2, tk;
+  HIP_TRY(bsk1.alloc(BSK1_ELEMS));
+  HIP_TRY(ksk.alloc(KSK_ELEMS));
+  HIP_TRY(bsk2.alloc(BSK2_ELEMS));
+  HIP_TRY(tk.alloc(TK_ELEMS));
+  OMR_TRY(omr_expand_detection_key_device(key, bsk1, ksk, bsk2, tk, nullptr));
+  const omr_detection_key_view full{bsk1, ksk, bsk2, tk};
+  return create_ctx(&full, device, out);
 }
 
 extern "C" void omr_ctx_destroy(omr_ctx *c) {

@@ -100,84 +100,103 @@ extern "C" omr_status omr_secret_export(const omr_secret_key_pack *sk, uint8_t *
 
 namespace omr {
 namespace {
-// RLWE encryption of zero with mask alpha, plus m*g in component `comp` of coefficient 0:
+// RLWE encryption of zero with mask alpha (uniform draws of `sa`) and noise from `se` (the same stream
+// for a plain key), plus m*g in component `comp` of coefficient 0:
 // row = (alpha + [comp==0] m g, alpha*s + e + [comp==1] m g). Writes canonical residues.
+// Seeded rows (s_fold = the ternary coefficients of s, out_a may be NULL) keep a = alpha, a function of
+// the public mask seed alone, and put the a-gadget into the body: b = alpha*s + e - m g s, the same
+// phase e - m g s as the row above.
 template <typename T>
-void ggsw_row(Stream &st, const Gaussian &gauss, const HostNtt &tab, const std::vector<uint64_t> &s_ntt,
-              const std::vector<uint64_t> &s_ntts, uint64_t mg, int comp, T *out_a, T *out_b,
-              const int8_t *sigma_s = nullptr, uint64_t sigma_scale = 0) {
+void ggsw_row(Stream &sa, Stream &se, const Gaussian &gauss, const HostNtt &tab,
+              const std::vector<uint64_t> &s_ntt, const std::vector<uint64_t> &s_ntts, uint64_t mg, int comp,
+              T *out_a, T *out_b, const int8_t *sigma_s = nullptr, uint64_t sigma_scale = 0,
+              const int8_t *s_fold = nullptr) {
   const int N = tab.N;
   const uint64_t q = tab.q;
   std::vector<uint64_t> a(N), t(N);
-  for (int j = 0; j < N; ++j) a[j] = st.uniform(q);
+  for (int j = 0; j < N; ++j) a[j] = sa.uniform(q);
   for (int j = 0; j < N; ++j) t[j] = a[j];
   tab.fwd(t.data());
   for (int j = 0; j < N; ++j) t[j] = tab.mul(t[j], s_ntt[j], s_ntts[j]);
   tab.inv(t.data());  // alpha * s
   for (int j = 0; j < N; ++j) {
-    uint64_t b = t[j] + to_mod(gauss.sample(st), q);
+    uint64_t b = t[j] + to_mod(gauss.sample(se), q);
     b = b >= q ? b - q : b;
     if (sigma_s && sigma_s[j]) {  // - sigma_g(s) * scale
       uint64_t c = mulmod(sigma_scale, (uint64_t)(sigma_s[j] < 0 ? q - 1 : 1), q);
       b = b >= c ? b - c : b + q - c;
     }
+    if (s_fold && comp == 0 && mg && s_fold[j]) {  // - m g s
+      const uint64_t c = s_fold[j] < 0 ? q - mg : mg;
+      b = b >= c ? b - c : b + q - c;
+    }
     t[j] = b;
   }
   if (mg) {
-    if (comp == 0) a[0] = (a[0] + mg) % q;
-    else t[0] = (t[0] + mg) % q;
+    if (comp == 1) t[0] = (t[0] + mg) % q;
+    else if (!s_fold) a[0] = (a[0] + mg) % q;
   }
   for (int j = 0; j < N; ++j) {
-    out_a[j] = (T)a[j];
+    if (out_a) out_a[j] = (T)a[j];
     out_b[j] = (T)t[j];
   }
 }
-}  // namespace
-}  // namespace omr
 
-// DetectionKey (key_gen/secret.rs:118-178).
-extern "C" omr_status omr_keygen_detection_key(const omr_secret_key_pack *sk, uint64_t seed,
-                                               uint32_t *bsk1, uint32_t *ksk, uint64_t *bsk2,
-                                               uint64_t *tk, int nthreads) {
-  if (!sk || !bsk1 || !ksk || !bsk2 || !tk)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_keygen_detection_key: NULL argument");
+// The first `n` accepted draws of Stream(mask_seed, dom, row).uniform(q): the mask of a seeded row.
+template <typename T>
+void mask_row(uint64_t mask_seed, uint32_t dom, uint64_t row, uint64_t q, int n, T *out) {
+  Stream st(mask_seed, dom, row);
+  for (int j = 0; j < n; ++j) out[j] = (T)st.uniform(q);
+}
+
+// Every row of a detection key. Plain (mask_seed NULL): one stream per row draws the mask and then the
+// noise, rows (a, b) in the layout of include/omr_gpu.h. Seeded: the mask from the public stream, the
+// noise from word 0 of the noise stream, and only the bodies are written (bsk1 [4096][1024],
+// ksk [27648], bsk2 [8040][2048], tk [275][2048]).
+omr_status keygen_rows(const omr_secret_key_pack *sk, uint64_t seed, const uint64_t *mask_seed, uint32_t *bsk1,
+                       uint32_t *ksk, uint64_t *bsk2, uint64_t *tk, int nthreads) {
+  const bool sd = mask_seed != nullptr;
+  const uint64_t ms = sd ? *mask_seed : 0;
   const Gaussian g1(SIGMA_BR1), gks(SIGMA_KS), g2(SIGMA_BR2), gt(SIGMA_TRACE);
   // BSK1: BlindRotationKey::generate(s0, NTT(s1), basis(q1,5,4), sigma 3.1859), :124-131
   parallel_for((size_t)N0 * 2 * D1, nthreads, [&](size_t row) {
     const size_t i = row / (2 * D1);
     const int r = (int)(row % (2 * D1));
-    Stream st(seed, DOM_BSK1, row);
+    Stream st(seed, sd ? DOM_BSK1_NOISE : DOM_BSK1, row), sm(ms, DOM_BSK1_MASK, row);
     const int k = r < D1 ? r : r - D1;
     const uint64_t mg = sk->s0[i] ? (1ull << (DROP1 + k * LOGB1)) : 0;
-    uint32_t *o = bsk1 + row * 2 * N1;
-    ggsw_row<uint32_t>(st, g1, ntt1(), sk->s1_ntt, sk->s1_ntts, mg, r < D1 ? 0 : 1, o, o + N1);
+    uint32_t *oa = sd ? nullptr : bsk1 + row * 2 * N1, *ob = sd ? bsk1 + row * N1 : oa + N1;
+    ggsw_row<uint32_t>(sd ? sm : st, st, g1, ntt1(), sk->s1_ntt, sk->s1_ntts, mg, r < D1 ? 0 : 1, oa, ob, nullptr, 0,
+                       sd ? sk->s1 : nullptr);
   });
   // KSK: NonPowOf2LweKeySwitchingKey::generate(s1 (-1 -> q1-1), s_int, ...), :133-147
   parallel_for((size_t)N1 * KS_DIGITS, nthreads, [&](size_t row) {
     const size_t i = row / KS_DIGITS;
     const int j = (int)(row % KS_DIGITS);
-    Stream st(seed, DOM_KSK, row);
-    uint32_t *o = ksk + row * (NI + 1);
+    Stream st(seed, sd ? DOM_KSK_NOISE : DOM_KSK, row), sm(ms, DOM_KSK_MASK, row);
+    Stream &sa = sd ? sm : st;
+    uint32_t *o = sd ? nullptr : ksk + row * (NI + 1);
     uint64_t b = 0;
     for (int c = 0; c < NI; ++c) {
-      uint64_t a = st.uniform(Q1);
-      o[c] = (uint32_t)a;
+      uint64_t a = sa.uniform(Q1);
+      if (o) o[c] = (uint32_t)a;
       if (sk->sint[c]) b += a;
     }
     b %= Q1;
     b = (b + to_mod(gks.sample(st), Q1)) % Q1;
     const uint64_t m = mulmod(to_mod(sk->s1[i], Q1), (1ull << j) % Q1, Q1);
-    o[NI] = (uint32_t)((b + m) % Q1);
+    (sd ? ksk[row] : o[NI]) = (uint32_t)((b + m) % Q1);
   });
   // BSK2: BlindRotationKey::generate(s_int, NTT(s2), basis(q2,7,6), sigma 0.3908), :149-156
   parallel_for((size_t)NI * 2 * D2, nthreads, [&](size_t row) {
     const size_t i = row / (2 * D2);
     const int r = (int)(row % (2 * D2));
-    Stream st(seed, DOM_BSK2, row);
+    Stream st(seed, sd ? DOM_BSK2_NOISE : DOM_BSK2, row), sm(ms, DOM_BSK2_MASK, row);
     const int k = r < D2 ? r : r - D2;
     const uint64_t mg = sk->sint[i] ? (1ull << (DROP2 + k * LOGB2)) : 0;
-    uint64_t *o = bsk2 + row * 2 * N2;
-    ggsw_row<uint64_t>(st, g2, ntt2(), sk->s2_ntt, sk->s2_ntts, mg, r < D2 ? 0 : 1, o, o + N2);
+    uint64_t *oa = sd ? nullptr : bsk2 + row * 2 * N2, *ob = sd ? bsk2 + row * N2 : oa + N2;
+    ggsw_row<uint64_t>(sd ? sm : st, st, g2, ntt2(), sk->s2_ntt, sk->s2_ntts, mg, r < D2 ? 0 : 1, oa, ob, nullptr, 0,
+                       sd ? sk->s2 : nullptr);
   });
   // TraceKey::new(s2, NTT(s2), basis(q2,2,None), sigma 0.3908), :158-165
   parallel_for((size_t)TRACE_STEPS * DT, nthreads, [&](size_t row) {
@@ -189,11 +208,70 @@ extern "C" omr_status omr_keygen_detection_key(const omr_secret_key_pack *sk, ui
       if (e < (uint32_t)N2) sg[e] = sk->s2[i];
       else sg[e - N2] = (int8_t)-sk->s2[i];
     }
-    Stream st(seed, DOM_TK, row);
-    uint64_t *o = tk + row * 2 * N2;
-    ggsw_row<uint64_t>(st, gt, ntt2(), sk->s2_ntt, sk->s2_ntts, 0, 1, o, o + N2, sg,
-                       (1ull << (2 * j)) % Q2);
+    Stream st(seed, sd ? DOM_TK_NOISE : DOM_TK, row), sm(ms, DOM_TK_MASK, row);
+    uint64_t *oa = sd ? nullptr : tk + row * 2 * N2, *ob = sd ? tk + row * N2 : oa + N2;
+    ggsw_row<uint64_t>(sd ? sm : st, st, gt, ntt2(), sk->s2_ntt, sk->s2_ntts, 0, 1, oa, ob, sg, (1ull << (2 * j)) % Q2);
   });
+  return OMR_OK;
+}
+
+// Masks of rows [first, first + rows) of component c into out + i * stride (elements of the component).
+template <typename T>
+void mask_rows(const KeyComponent &c, uint64_t mask_seed, size_t first, size_t rows, T *out, size_t stride,
+               int nthreads) {
+  const uint64_t q = c.level == 1 ? Q1 : Q2;
+  parallel_for(rows, nthreads, [&](size_t i) { mask_row<T>(mask_seed, c.mask_dom, first + i, q, c.masks, out + i * stride); });
+}
+
+// One component of a seeded key -> rows (mask, body) in the standard layout.
+template <typename T>
+void expand_component(int comp, uint64_t mask_seed, const T *body, T *out, int nthreads) {
+  const KeyComponent &c = *key_component(comp);
+  mask_rows<T>(c, mask_seed, 0, c.rows, out, (size_t)c.row_elems, nthreads);
+  parallel_for(c.rows, nthreads, [&](size_t r) {
+    memcpy(out + r * c.row_elems + c.masks, body + r * c.body(), c.body() * sizeof(T));
+  });
+}
+}  // namespace
+}  // namespace omr
+
+// DetectionKey (key_gen/secret.rs:118-178).
+extern "C" omr_status omr_keygen_detection_key(const omr_secret_key_pack *sk, uint64_t seed,
+                                               uint32_t *bsk1, uint32_t *ksk, uint64_t *bsk2,
+                                               uint64_t *tk, int nthreads) {
+  if (!sk || !bsk1 || !ksk || !bsk2 || !tk)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_keygen_detection_key: NULL argument");
+  return keygen_rows(sk, seed, nullptr, bsk1, ksk, bsk2, tk, nthreads);
+}
+
+// Seeded detection key (include/omr_gpu.h): the bodies of a key whose masks come from mask_seed.
+extern "C" omr_status omr_keygen_seeded_key(const omr_secret_key_pack *sk, uint64_t seed, uint64_t mask_seed,
+                                            uint32_t *bsk1_b, uint32_t *ksk_b, uint64_t *bsk2_b,
+                                            uint64_t *tk_b, int nthreads) {
+  if (!sk || !bsk1_b || !ksk_b || !bsk2_b || !tk_b)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_keygen_seeded_key: NULL argument");
+  return keygen_rows(sk, seed, &mask_seed, bsk1_b, ksk_b, bsk2_b, tk_b, nthreads);
+}
+
+extern "C" omr_status omr_expand_detection_key(const omr_seeded_key_view *key, uint32_t *bsk1, uint32_t *ksk,
+                                               uint64_t *bsk2, uint64_t *tk, int nthreads) {
+  if (!key || !key->bsk1_b || !key->ksk_b || !key->bsk2_b || !key->trace_key_b || !bsk1 || !ksk || !bsk2 || !tk)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_expand_detection_key: NULL argument");
+  expand_component<uint32_t>(OMR_KEY_BSK1, key->mask_seed, key->bsk1_b, bsk1, nthreads);
+  expand_component<uint32_t>(OMR_KEY_KSK, key->mask_seed, key->ksk_b, ksk, nthreads);
+  expand_component<uint64_t>(OMR_KEY_BSK2, key->mask_seed, key->bsk2_b, bsk2, nthreads);
+  expand_component<uint64_t>(OMR_KEY_TRACE, key->mask_seed, key->trace_key_b, tk, nthreads);
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_key_masks(uint64_t mask_seed, int component, size_t first_row, size_t rows, void *out) {
+  const KeyComponent *c = key_component(component);
+  if (!c) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_key_masks: no such component");
+  if (first_row > c->rows || rows > c->rows - first_row)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_key_masks: row range beyond the component");
+  if (rows && !out) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_key_masks: out is NULL");
+  if (c->level == 1) mask_rows<uint32_t>(*c, mask_seed, first_row, rows, (uint32_t *)out, (size_t)c->masks, 0);
+  else mask_rows<uint64_t>(*c, mask_seed, first_row, rows, (uint64_t *)out, (size_t)c->masks, 0);
   return OMR_OK;
 }
 

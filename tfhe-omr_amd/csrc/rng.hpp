@@ -15,7 +15,28 @@ namespace omr {
 enum Domain : uint32_t {
   DOM_S0 = 1, DOM_S1 = 2, DOM_SINT = 3, DOM_S2 = 4, DOM_PK_A = 5, DOM_PK_E = 6,
   DOM_BSK1 = 10, DOM_KSK = 11, DOM_BSK2 = 12, DOM_TK = 13, DOM_CLUE = 20,
+  // seeded detection keys (include/omr_gpu.h): the masks come from the public mask seed, the noise
+  // from the secret seed in domains of its own, so that no plain key generated from the same seed
+  // publishes, as its `a` words, the words that feed a seeded key's noise
+  DOM_BSK1_MASK = 30, DOM_KSK_MASK = 31, DOM_BSK2_MASK = 32, DOM_TK_MASK = 33,
+  DOM_BSK1_NOISE = 40, DOM_KSK_NOISE = 41, DOM_BSK2_NOISE = 42, DOM_TK_NOISE = 43,
 };
+
+// A detection-key component (omr_key_component order) as rows of `masks` uniform words followed by
+// the body: row_elems - masks words (N for an RLWE row, 1 for a key-switching row).
+struct KeyComponent {
+  uint32_t mask_dom;
+  size_t rows;
+  int masks, row_elems, level;  // level 1: u32 mod q1, level 2: u64 mod q2
+  size_t body() const { return (size_t)(row_elems - masks); }
+};
+inline const KeyComponent *key_component(int c) {
+  static const KeyComponent t[4] = {{DOM_BSK1_MASK, (size_t)N0 * 2 * D1, N1, 2 * N1, 1},
+                                    {DOM_KSK_MASK, (size_t)N1 * KS_DIGITS, NI, NI + 1, 1},
+                                    {DOM_BSK2_MASK, (size_t)NI * 2 * D2, N2, 2 * N2, 2},
+                                    {DOM_TK_MASK, (size_t)TRACE_STEPS * DT, N2, 2 * N2, 2}};
+  return c >= 0 && c < 4 ? &t[c] : nullptr;
+}
 
 class Stream {
  public:

@@ -4,7 +4,8 @@
 // encode_pertinent_payloads, client-side retrieval, and a check that exactly the pertinent
 // indices and their payloads come back.
 //
-//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--host-only]
+//   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
+//           [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -15,6 +16,10 @@
 // omr_digest_enable_bitmap; omr_retrieve_bitmap), which needs no pertinent count, instead of the index
 // digest; the payloads are then solved for those indices. With --host-only it checks the bitmap's layout
 // on the host (omr_bitmap_ct_count, omr_bitmap_indices on the board's own pertinent set).
+// --seeded generates the detection key in its seeded form (omr_keygen_seeded_key: the bodies and a public
+// mask seed, 146 MiB instead of 363) and builds the detector through omr_ctx_create_seeded, which expands
+// it on the device. With --host-only the key is expanded on the host (omr_expand_detection_key) and its
+// masks are checked against omr_key_masks.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -34,6 +39,7 @@ namespace {
 constexpr size_t N0 = 512, CLUES = 7, N2 = 2048, PAYLOAD = 612;
 constexpr size_t BSK1 = 512ull * 8 * 2 * 1024, KSK = 1024ull * 27 * 671, BSK2 = 670ull * 12 * 2 * 2048,
                  TK = 11ull * 25 * 2 * 2048;
+constexpr size_t BSK1_B = BSK1 / 2, KSK_B = 1024ull * 27, BSK2_B = BSK2 / 2, TK_B = TK / 2;  // seeded bodies
 
 using clk = std::chrono::steady_clock;
 double secs(clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); }
@@ -55,7 +61,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false, bitmap = false;
+  bool audit = false, bitmap = false, seeded = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if ((a == "-p" || a == "--payload-count") && i + 1 < argc) D = std::max<size_t>(1, std::stoull(argv[++i]));
@@ -64,10 +70,11 @@ int main(int argc, char **argv) {
     else if (a == "--session" && i + 1 < argc) session_piece = std::max<size_t>(1, std::stoull(argv[++i]));
     else if (a == "--audit") audit = true;
     else if (a == "--bitmap") bitmap = true;
+    else if (a == "--seeded") seeded = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--host-only]\n",
+                   "[--seeded] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -79,10 +86,41 @@ int main(int argc, char **argv) {
   omr_secret_key_pack *pa = nullptr, *pb = nullptr;
   CHECK(omr_keygen_secret(seed ^ 0xA, &pa));
   CHECK(omr_keygen_secret(seed ^ 0xB, &pb));
-  std::vector<uint32_t> bsk1(BSK1), ksk(KSK);
-  std::vector<uint64_t> bsk2(BSK2), tk(TK);
-  CHECK(omr_keygen_detection_key(pa, seed ^ 0xD, bsk1.data(), ksk.data(), bsk2.data(), tk.data(), 0));
-  std::printf("keygen time: %.3f s\n", secs(t));
+  // full key, or with --seeded the bodies alone (the full key only where the host expands it)
+  const bool full = !seeded || host_only;
+  std::vector<uint32_t> bsk1(full ? BSK1 : 0), ksk(full ? KSK : 0), bsk1_b(seeded ? BSK1_B : 0), ksk_b(seeded ? KSK_B : 0);
+  std::vector<uint64_t> bsk2(full ? BSK2 : 0), tk(full ? TK : 0), bsk2_b(seeded ? BSK2_B : 0), tk_b(seeded ? TK_B : 0);
+  const omr_seeded_key_view sview{bsk1_b.data(), ksk_b.data(), bsk2_b.data(), tk_b.data(), seed ^ 0x5EED};
+  if (seeded) {
+    CHECK(omr_keygen_seeded_key(pa, seed ^ 0xD, sview.mask_seed, bsk1_b.data(), ksk_b.data(), bsk2_b.data(), tk_b.data(), 0));
+    std::printf("seeded keygen time: %.3f s (%zu bytes on the wire, %zu expanded)\n", secs(t),
+                BSK1_B * 4 + KSK_B * 4 + BSK2_B * 8 + TK_B * 8 + 8, BSK1 * 4 + KSK * 4 + BSK2 * 8 + TK * 8);
+  } else {
+    CHECK(omr_keygen_detection_key(pa, seed ^ 0xD, bsk1.data(), ksk.data(), bsk2.data(), tk.data(), 0));
+    std::printf("keygen time: %.3f s\n", secs(t));
+  }
+  if (seeded && host_only) {
+    t = clk::now();
+    CHECK(omr_expand_detection_key(&sview, bsk1.data(), ksk.data(), bsk2.data(), tk.data(), 0));
+    std::printf("host expansion time: %.3f s\n", secs(t));
+    // the last row of every component: a = omr_key_masks, b = the body
+    std::vector<uint32_t> m1(1024), mk(670);
+    std::vector<uint64_t> m2(2048), mt(2048);
+    CHECK(omr_key_masks(sview.mask_seed, OMR_KEY_BSK1, 4095, 1, m1.data()));
+    CHECK(omr_key_masks(sview.mask_seed, OMR_KEY_KSK, 27647, 1, mk.data()));
+    CHECK(omr_key_masks(sview.mask_seed, OMR_KEY_BSK2, 8039, 1, m2.data()));
+    CHECK(omr_key_masks(sview.mask_seed, OMR_KEY_TRACE, 274, 1, mt.data()));
+    const bool ok = std::equal(m1.begin(), m1.end(), &bsk1[BSK1 - 2048]) && std::equal(mk.begin(), mk.end(), &ksk[KSK - 671]) &&
+                    std::equal(m2.begin(), m2.end(), &bsk2[BSK2 - 4096]) && std::equal(mt.begin(), mt.end(), &tk[TK - 4096]) &&
+                    std::equal(&bsk1[BSK1 - 1024], &bsk1[BSK1], &bsk1_b[BSK1_B - 1024]) && ksk[KSK - 1] == ksk_b[KSK_B - 1] &&
+                    std::equal(&bsk2[BSK2 - 2048], &bsk2[BSK2], &bsk2_b[BSK2_B - 2048]) &&
+                    std::equal(&tk[TK - 2048], &tk[TK], &tk_b[TK_B - 2048]);
+    if (!ok) {
+      std::printf("Fail: the expanded key is not (omr_key_masks, body)\nFAILED\n");
+      return 1;
+    }
+    std::printf("host-only: seeded key expands to (omr_key_masks, body) rows\n");
+  }
 
   // pertinent = first min(D, 50) of a shuffle (omr.rs:103-113)
   const size_t pert_count = std::min<size_t>(D, 50);
@@ -148,7 +186,10 @@ int main(int argc, char **argv) {
   // Detector::new + detect over the board (omr.rs:160-164)
   omr_ctx *ctx = nullptr;
   omr_detection_key_view view{bsk1.data(), ksk.data(), bsk2.data(), tk.data()};
-  CHECK(omr_ctx_create(&view, device, &ctx));
+  t = clk::now();
+  if (seeded) CHECK(omr_ctx_create_seeded(&sview, device, &ctx));
+  else CHECK(omr_ctx_create(&view, device, &ctx));
+  std::printf("detector creation time: %.3f s (%s)\n", secs(t), seeded ? "seeded key, expanded on the device" : "full key");
   const uint32_t n_idx = rp.max_encode_indices_cipher_count, n_pay = rp.cmb_cipher_count;
   omr_auditor *aud = nullptr;
   if (audit) CHECK(omr_auditor_create(pa, device, &aud));

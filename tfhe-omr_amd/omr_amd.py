@@ -25,6 +25,15 @@ BSK1_SHAPE = (N0, 8, 2, N1)
 KSK_SHAPE = (N1, KS_DIGITS, NI + 1)
 BSK2_SHAPE = (NI, 12, 2, N2)
 TK_SHAPE = (TRACE_STEPS, TRACE_DIGITS, 2, N2)
+# seeded detection key (include/omr_gpu.h): the bodies, and per component (omr_key_component order)
+# the rows, the masks per row and the element type
+BSK1_B_SHAPE = (N0, 8, N1)
+KSK_B_SHAPE = (N1, KS_DIGITS)
+BSK2_B_SHAPE = (NI, 12, N2)
+TK_B_SHAPE = (TRACE_STEPS, TRACE_DIGITS, N2)
+KEY_BSK1, KEY_KSK, KEY_BSK2, KEY_TRACE = 0, 1, 2, 3
+KEY_COMPONENTS = ((N0 * 8, N1, np.uint32), (N1 * KS_DIGITS, NI, np.uint32), (NI * 12, N2, np.uint64),
+                  (TRACE_STEPS * TRACE_DIGITS, N2, np.uint64))
 
 _u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
@@ -45,6 +54,11 @@ class _RetrievalParams(C.Structure):
 
 class _KeyView(C.Structure):
     _fields_ = [("bsk1", C.c_void_p), ("ksk", C.c_void_p), ("bsk2", C.c_void_p), ("trace_key", C.c_void_p)]
+
+
+class _SeededKeyView(C.Structure):
+    _fields_ = [("bsk1_b", C.c_void_p), ("ksk_b", C.c_void_p), ("bsk2_b", C.c_void_p), ("trace_key_b", C.c_void_p),
+                ("mask_seed", C.c_uint64)]
 
 
 class _Timing(C.Structure):
@@ -85,6 +99,15 @@ EXPORTS = {
                                        C.c_void_p]),
     "omr_keygen_detection_key_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),
+    "omr_keygen_seeded_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _u32p, _u32p, _u64p, _u64p, C.c_int]),
+    "omr_keygen_seeded_key_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "omr_expand_detection_key": (C.c_int, [C.POINTER(_SeededKeyView), _u32p, _u32p, _u64p, _u64p, C.c_int]),
+    "omr_expand_detection_key_device": (C.c_int, [C.POINTER(_SeededKeyView), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "omr_key_masks": (C.c_int, [C.c_uint64, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "omr_key_masks_device": (C.c_int, [C.c_uint64, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "omr_ctx_create_seeded": (C.c_int, [C.POINTER(_SeededKeyView), C.c_int, C.POINTER(C.c_void_p)]),
     "omr_get_retrieval_params": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(_RetrievalParams)]),
     "omr_payload_weights": (C.c_int, [_u8p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u16p]),
     "omr_ctx_create": (C.c_int, [C.POINTER(_KeyView), C.c_int, C.POINTER(C.c_void_p)]),
@@ -226,6 +249,61 @@ class DetectionKey:
         return sum(a.nbytes for a in (self.bsk1, self.ksk, self.bsk2, self.trace_key))
 
 
+@dataclass
+class SeededKey:
+    """The seeded form of a detection key (include/omr_gpu.h): the bodies and the public mask seed,
+    153,120,776 bytes instead of 380,227,584."""
+    bsk1_b: np.ndarray
+    ksk_b: np.ndarray
+    bsk2_b: np.ndarray
+    trace_key_b: np.ndarray
+    mask_seed: int
+
+    def size(self) -> int:
+        return sum(a.nbytes for a in (self.bsk1_b, self.ksk_b, self.bsk2_b, self.trace_key_b)) + 8
+
+    def _view(self) -> "_SeededKeyView":
+        for a, shape, dt in ((self.bsk1_b, BSK1_B_SHAPE, np.uint32), (self.ksk_b, KSK_B_SHAPE, np.uint32),
+                             (self.bsk2_b, BSK2_B_SHAPE, np.uint64), (self.trace_key_b, TK_B_SHAPE, np.uint64)):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise OmrError(f"seeded key body has shape {a.shape} {a.dtype}, expected {shape} {dt}")
+        return _SeededKeyView(self.bsk1_b.ctypes.data, self.ksk_b.ctypes.data, self.bsk2_b.ctypes.data,
+                              self.trace_key_b.ctypes.data, self.mask_seed)
+
+    def expand(self, nthreads: int = 0) -> DetectionKey:
+        """omr_expand_detection_key: the full key on the host."""
+        dk = DetectionKey(np.empty(BSK1_SHAPE, np.uint32), np.empty(KSK_SHAPE, np.uint32),
+                          np.empty(BSK2_SHAPE, np.uint64), np.empty(TK_SHAPE, np.uint64))
+        view = self._view()
+        _check(lib().omr_expand_detection_key(C.byref(view), dk.bsk1.reshape(-1), dk.ksk.reshape(-1),
+                                              dk.bsk2.reshape(-1), dk.trace_key.reshape(-1), nthreads),
+               "omr_expand_detection_key")
+        return dk
+
+
+def expand_detection_key_device(d_bodies, mask_seed: int, d_bsk1: int, d_ksk: int, d_bsk2: int, d_trace_key: int,
+                                stream: int = 0) -> None:
+    """omr_expand_detection_key_device: d_bodies is a SeededKey (host bodies) or four raw pointers
+    (bsk1_b, ksk_b, bsk2_b, trace_key_b; host or device memory); the full key goes to device buffers."""
+    view = d_bodies._view() if isinstance(d_bodies, SeededKey) else _SeededKeyView(*d_bodies, mask_seed)
+    _check(lib().omr_expand_detection_key_device(C.byref(view), d_bsk1, d_ksk, d_bsk2, d_trace_key, stream or None),
+           "omr_expand_detection_key_device")
+
+
+def key_masks(mask_seed: int, component: int, first_row: int, rows: int) -> np.ndarray:
+    """omr_key_masks: the masks [rows][N] of a row range of one component of a seeded key (host)."""
+    _, n, dt = KEY_COMPONENTS[component] if 0 <= component < 4 else (0, 1, np.uint32)
+    out = np.empty((max(rows, 0), n), dt)
+    _check(lib().omr_key_masks(mask_seed, component, first_row, rows, out.ctypes.data), "omr_key_masks")
+    return out
+
+
+def key_masks_device(mask_seed: int, component: int, first_row: int, rows: int, d_out: int, stream: int = 0) -> None:
+    """omr_key_masks_device: the same rows into a device buffer; returns when the stream is done."""
+    _check(lib().omr_key_masks_device(mask_seed, component, first_row, rows, d_out or None, stream or None),
+           "omr_key_masks_device")
+
+
 class SecretKeyPack:
     """KeyGen::generate_secret_key / SecretKeyPack (key_gen/secret.rs:46-209), seeded."""
 
@@ -260,6 +338,15 @@ class SecretKeyPack:
                                               tk.reshape(-1), nthreads), "omr_keygen_detection_key")
         return DetectionKey(bsk1, ksk, bsk2, tk)
 
+    def generate_seeded_key(self, seed: int, mask_seed: int, nthreads: int = 0) -> SeededKey:
+        """omr_keygen_seeded_key: the bodies of the key whose masks come from the public mask_seed."""
+        sk = SeededKey(np.empty(BSK1_B_SHAPE, np.uint32), np.empty(KSK_B_SHAPE, np.uint32),
+                       np.empty(BSK2_B_SHAPE, np.uint64), np.empty(TK_B_SHAPE, np.uint64), mask_seed)
+        _check(lib().omr_keygen_seeded_key(self._h, seed, mask_seed, sk.bsk1_b.reshape(-1), sk.ksk_b.reshape(-1),
+                                           sk.bsk2_b.reshape(-1), sk.trace_key_b.reshape(-1), nthreads),
+               "omr_keygen_seeded_key")
+        return sk
+
     def gen_clues(self, seed: int, first: int, count: int, nthreads: int = 0):
         """Sender::gen_clues for global message indices [first, first+count)."""
         a = np.empty((count, N0), np.uint16)
@@ -279,15 +366,21 @@ class SecretKeyPack:
         _check(lib().omr_keygen_detection_key_device(self._h, seed, d_bsk1, d_ksk, d_bsk2, d_trace_key,
                                                      stream or None), "omr_keygen_detection_key_device")
 
+    def generate_seeded_key_device(self, seed: int, mask_seed: int, d_bsk1_b: int, d_ksk_b: int, d_bsk2_b: int,
+                                   d_trace_key_b: int, stream: int = 0):
+        _check(lib().omr_keygen_seeded_key_device(self._h, seed, mask_seed, d_bsk1_b, d_ksk_b, d_bsk2_b,
+                                                  d_trace_key_b, stream or None), "omr_keygen_seeded_key_device")
+
 
 # ---- on-disk container (the reference has no serialization) ----------------
 # Little-endian: b"OMRF" | u32 version = 1 | u32 kind | u32 n_arrays | n_arrays x
 # {u32 dtype (1 = u16, 2 = u32, 3 = u64), u32 ndim, u64 dims[4]} | arrays in order, each starting
 # at a 64-byte aligned offset, C order. Kinds: 1 detection key (bsk1, ksk, bsk2, trace_key in the
 # ABI layout of include/omr_gpu.h), 2 clues (clue_a [D][512], clue_b [D][7], first_index [1]),
-# 3 NttRlweCiphertexts (u64 [n][2][2048], e.g. a pertinency vector or a digest).
+# 3 NttRlweCiphertexts (u64 [n][2][2048], e.g. a pertinency vector or a digest), 4 seeded detection key
+# (bsk1_b, ksk_b, bsk2_b, trace_key_b in the layout of include/omr_gpu.h, then mask_seed u64 [1]).
 _FILE_MAGIC, _FILE_VERSION = b"OMRF", 1
-KIND_DETECTION_KEY, KIND_CLUES, KIND_CIPHERTEXTS = 1, 2, 3
+KIND_DETECTION_KEY, KIND_CLUES, KIND_CIPHERTEXTS, KIND_SEEDED_KEY = 1, 2, 3, 4
 _DT = {np.dtype(np.uint16): 1, np.dtype(np.uint32): 2, np.dtype(np.uint64): 3}
 _DT_INV = {v: k for k, v in _DT.items()}
 
@@ -336,6 +429,16 @@ def save_detection_key(path: str, dk: "DetectionKey") -> None:
 def load_detection_key(path: str) -> "DetectionKey":
     b1, k, b2, t = read_arrays(path, KIND_DETECTION_KEY)
     return DetectionKey(bsk1=np.array(b1), ksk=np.array(k), bsk2=np.array(b2), trace_key=np.array(t))
+
+
+def save_seeded_key(path: str, sk: "SeededKey") -> None:
+    write_arrays(path, KIND_SEEDED_KEY, [sk.bsk1_b, sk.ksk_b, sk.bsk2_b, sk.trace_key_b,
+                                         np.array([sk.mask_seed], np.uint64)])
+
+
+def load_seeded_key(path: str) -> "SeededKey":
+    b1, k, b2, t, seed = read_arrays(path, KIND_SEEDED_KEY)
+    return SeededKey(np.array(b1), np.array(k), np.array(b2), np.array(t), int(seed[0]))
 
 
 def save_clues(path: str, clue_a, clue_b, first: int = 0) -> None:
@@ -587,6 +690,21 @@ class Detector:
         view = _KeyView(d_bsk1, d_ksk, d_bsk2, d_trace_key)
         h = C.c_void_p()
         _check(lib().omr_ctx_create(C.byref(view), device, C.byref(h)), "omr_ctx_create")
+        self._h = h
+        self.device = device
+        _bind_destroy()
+        _LIVE_DETECTORS.add(self)
+        return self
+
+    @classmethod
+    def from_seeded_key(cls, key, device: int = 0, mask_seed: int = 0):
+        """Detector from a seeded key (omr_ctx_create_seeded): a SeededKey with host bodies, or four raw
+        pointers (bsk1_b, ksk_b, bsk2_b, trace_key_b; host memory or HBM of `device`) and the mask_seed.
+        The key is expanded on the device; the expanded copy is freed before this returns."""
+        self = cls.__new__(cls)
+        view = key._view() if isinstance(key, SeededKey) else _SeededKeyView(*key, mask_seed)
+        h = C.c_void_p()
+        _check(lib().omr_ctx_create_seeded(C.byref(view), device, C.byref(h)), "omr_ctx_create_seeded")
         self._h = h
         self.device = device
         _bind_destroy()
