@@ -572,6 +572,90 @@ omr_status omr_digest_merge_bitmap(omr_digest *dg, const uint64_t *bitmap_cts);
 void omr_digest_destroy(omr_digest *dg);
 
 /* ---------------------------------------------------------------------------------------
+ * Compact ciphertexts (none in the reference): the form in which a digest travels to the recipient. A
+ * digest ciphertext leaves the detector with far more precision than decoding needs (max |r| / q2 of
+ * 2.2e-5 for a 7-ciphertext digest and 2.4e-5 for a full bitmap ciphertext; decoding fails
+ * at 0.5), so it is modulus-switched from q2 to Q = 2^bits and sent at `bits` bits per coefficient:
+ * 512 * bits bytes instead of 32,768 (12,288 at 24 bits, 10,240 at 20). `bits` is any integer in
+ * [OMR_COMPACT_MIN_BITS, OMR_COMPACT_MAX_BITS]; p = 257.
+ *
+ * Compact. The input is an NttRlweCiphertext u64 [2][2048]; words are reduced mod q2 first, as the
+ * auditor does. For h in {a, b} let x_h be the coefficient form: the polynomial whose NTT in the
+ * convention above is the input row, canonical in [0, q2), in natural coefficient order. Per coefficient
+ *   y = floor((2 x Q + q2) / (2 q2)) mod Q.
+ * q2 is odd, so there are no ties; x close to q2 rounds to Q and wraps to 0.
+ *
+ * Packing. One compact ciphertext is 512 * bits bytes: the 2,048 values of a, then those of b, as one
+ * little-endian bit stream per polynomial (256 * bits bytes each). Value i occupies stream bits
+ * [i bits, (i + 1) bits); stream bit k is bit (k mod 8) of byte k / 8. 512 * bits is a multiple of 16, so
+ * every ciphertext of an array starts on a 16-byte boundary when the array does.
+ *
+ * Expand. Per value x' = (y q2 + Q / 2) >> bits, which lies in [0, q2); then the forward NTT. The result
+ * is an ordinary NttRlweCiphertext under the same key, canonical, and every client entry point takes it
+ * unchanged: omr_retrieve_indices, omr_retrieve_payloads, omr_retrieve_bitmap, omr_decrypt_decode, the
+ * auditor.
+ *
+ * Bound. Write the compacted phase in units of Q. Each of the 4,096 roundings errs by at most 1/2; the
+ * a-side errors reach the phase through a negacyclic product with the ternary s2, so compaction adds
+ * delta with |delta_j| <= (1 + ||s2||_1) / 2 in units of Q. Expansion rounds once more per value and adds
+ * at most the same amount in units of q2. In the auditor's residual units (r = p c - t' q2), as long as
+ * the decoded value does not change,
+ *   |r_expanded| <= |r_original| + R(bits),  R(bits) = ceil(p (1 + ||s2||_1) (q2 + Q) / (2 Q))
+ * (omr_compact_residual_bound). Decoding of a compacted ciphertext is therefore proven correct when
+ * max |r_original| + R(bits) <= (q2 - 1) / 2. With ||s2||_1 <= 2048, R / q2 is 0.0157 at 24 bits, 0.0628
+ * at 22, 0.2511 at 20 and 0.502 at 19: 19 bits is not provable for a worst-case key. A real key has
+ * ||s2||_1 near 1,365, and the recipient knows its own. The server cannot evaluate the bound (it has no
+ * secret); it compacts to the width the recipient asked for.
+ *
+ * A compacted ciphertext is for decoding only: it no longer has the headroom of a pertinency ciphertext,
+ * so it must not be fed to omr_encode_* or merged into a digest (merging stays in the full form).
+ * ------------------------------------------------------------------------------------- */
+#define OMR_COMPACT_MIN_BITS 16
+#define OMR_COMPACT_MAX_BITS 32
+/* 512 * bits; OMR_ERR_INVALID_ARGUMENT for bits out of range (as in every call below, before anything
+ * else is looked at or enqueued) */
+omr_status omr_compact_ct_bytes(int bits, size_t *bytes);
+/* R(bits) for the pack's s2 (a 128-bit product on the host) */
+omr_status omr_compact_residual_bound(const omr_secret_key_pack *sk, int bits, uint64_t *R);
+/* The CPU statement of both directions (no GPU): out is n x 512 bits bytes, cts_out u64 [n][2][2048].
+ * nthreads <= 0: the host's cores, at most 16. n = 0 does nothing; NULL with n > 0 is invalid. */
+omr_status omr_compact_cts_cpu(const uint64_t *cts, size_t n, int bits, void *out, int nthreads);
+omr_status omr_compact_expand_cpu(const void *packed, size_t n, int bits, uint64_t *cts_out, int nthreads);
+/* Server side, on the context's device: needs the context's level-2 inverse twiddles and nothing else
+ * (no key, no scratch lease), so it runs beside any other call on the context. Device buffers, 16-byte
+ * aligned (OMR_ERR_INVALID_ARGUMENT otherwise, and for NULL with n > 0), enqueued on hip_stream
+ * (NULL = null stream); returns once enqueued; n = 0 does nothing. The same bits as omr_compact_cts_cpu. */
+omr_status omr_compact_cts_device(omr_ctx *ctx, const uint64_t *d_cts, size_t n, int bits, void *d_out,
+                                  void *hip_stream);
+/* the same on host buffers, staged in pieces on the context's own stream; returns when done */
+omr_status omr_compact_cts(omr_ctx *ctx, const uint64_t *cts, size_t n, int bits, void *out);
+/* knobs, results identical for every setting: workgroups of compact_kernel's grid, which strides over the
+ * ciphertexts (0 = default, six per compute unit; also used by omr_digest_read_compact), and the
+ * ciphertexts staged per piece by omr_compact_cts (0 = default 2,048 = 64 MiB) */
+omr_status omr_ctx_set_compact_grid(omr_ctx *ctx, unsigned workgroups);
+omr_status omr_ctx_set_compact_staging(omr_ctx *ctx, size_t max_ciphertexts);
+/* Client side, on an auditor, which holds the level-2 forward twiddles for this. Device buffers of the
+ * auditor's device, 16-byte aligned, enqueued on hip_stream; returns once enqueued; n = 0 does nothing.
+ * The same bits as omr_compact_expand_cpu. omr_auditor_set_grid sets expand_kernel's grid too (0 = six
+ * per compute unit). */
+omr_status omr_compact_expand_device(omr_auditor *aud, const void *d_packed, size_t n, int bits,
+                                     uint64_t *d_cts, void *hip_stream);
+/* omr_audit over compact ciphertexts in host memory: staged in pieces (omr_auditor_set_staging), each
+ * expanded on the device and audited there. Results identical to omr_audit over omr_compact_expand_cpu's
+ * output; summary is added into. */
+omr_status omr_audit_compact(omr_auditor *aud, const void *packed, size_t n, int bits, omr_ct_audit *records,
+                             uint16_t *decoded, omr_audit_summary *summary);
+/* The session's digest in compact form: idx_packed index_ct x 512 bits bytes, pay_packed payload_ct x,
+ * bitmap_packed omr_bitmap_ct_count(all) x; any pointer may be NULL. bitmap_packed non-NULL on a session
+ * without a bitmap is OMR_ERR_INVALID_ARGUMENT. Synchronises, takes a pending hand-off error and follows
+ * the poisoning rules exactly as omr_digest_read does; then compacts the running digest on the device and
+ * copies only the packed bytes: the same bits as omr_compact_cts_cpu of omr_digest_read /
+ * omr_digest_read_bitmap. The running digest is not modified: later updates, reads and merges behave as
+ * before. */
+omr_status omr_digest_read_compact(omr_digest *dg, int bits, void *idx_packed, void *pay_packed,
+                                   void *bitmap_packed);
+
+/* ---------------------------------------------------------------------------------------
  * Stage entry points (for parity tests and per-stage benchmarks, benches/two_level_bs.rs).
  * Host buffers.
  * ------------------------------------------------------------------------------------- */

@@ -286,6 +286,25 @@ pub mod ffi {
                                    all_payloads_count: usize, indices: *mut usize, cap: usize,
                                    found: *mut usize) -> OmrStatus;
 
+        // compact ciphertexts (none in the reference): q2 -> 2^bits, bit-packed, 512 * bits bytes each
+        pub fn omr_compact_ct_bytes(bits: c_int, bytes: *mut usize) -> OmrStatus;
+        pub fn omr_compact_residual_bound(sk: *const OmrSecretKeyPack, bits: c_int, r: *mut u64) -> OmrStatus;
+        pub fn omr_compact_cts_cpu(cts: *const u64, n: usize, bits: c_int, out: *mut c_void, nthreads: c_int) -> OmrStatus;
+        pub fn omr_compact_expand_cpu(packed: *const c_void, n: usize, bits: c_int, cts_out: *mut u64,
+                                      nthreads: c_int) -> OmrStatus;
+        pub fn omr_compact_cts_device(ctx: *mut OmrCtx, d_cts: *const u64, n: usize, bits: c_int, d_out: *mut c_void,
+                                      hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_compact_cts(ctx: *mut OmrCtx, cts: *const u64, n: usize, bits: c_int, out: *mut c_void) -> OmrStatus;
+        pub fn omr_ctx_set_compact_grid(ctx: *mut OmrCtx, workgroups: c_uint) -> OmrStatus;
+        pub fn omr_ctx_set_compact_staging(ctx: *mut OmrCtx, max_ciphertexts: usize) -> OmrStatus;
+        pub fn omr_compact_expand_device(aud: *mut OmrAuditor, d_packed: *const c_void, n: usize, bits: c_int,
+                                         d_cts: *mut u64, hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_audit_compact(aud: *mut OmrAuditor, packed: *const c_void, n: usize, bits: c_int,
+                                 records: *mut OmrCtAudit, decoded: *mut u16,
+                                 summary: *mut OmrAuditSummary) -> OmrStatus;
+        pub fn omr_digest_read_compact(dg: *mut OmrDigest, bits: c_int, idx_packed: *mut c_void,
+                                       pay_packed: *mut c_void, bitmap_packed: *mut c_void) -> OmrStatus;
+
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
                                lwe_int: *mut u32) -> OmrStatus;
@@ -637,7 +656,33 @@ impl GpuDetector {
         Ok(out.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect())
     }
 
-    /// The same on device buffers (`omr_encode_bitmap_device`), enqueued on `hip_stream`.
+    /// Ciphertexts in compact form through the device (`omr_compact_cts`): `512 * bits` bytes each, the
+    /// bits of `compact_cts_cpu`.
+    pub fn compact_cts(&self, cts: &[NttRlwe], bits: i32) -> Result<Vec<u8>, OmrError> {
+        let flat = NttRlwe::flatten(cts);
+        let mut out = vec![0u8; cts.len() * compact_ct_bytes(bits)?];
+        check(unsafe { omr_compact_cts(self.ctx, flat.as_ptr(), cts.len(), bits as c_int, out.as_mut_ptr() as *mut c_void) })?;
+        Ok(out)
+    }
+
+    /// The same on device buffers (`omr_compact_cts_device`), enqueued on `hip_stream`.
+    ///
+    /// # Safety
+    /// `d_cts` must be device memory of `n` ciphertexts and `d_out` of `n * 512 * bits` bytes, both
+    /// 16-byte aligned and valid until the stream has run the work.
+    pub unsafe fn compact_cts_device(&self, d_cts: *const u64, n: usize, bits: i32, d_out: *mut c_void,
+                                     hip_stream: *mut c_void) -> Result<(), OmrError> {
+        check(omr_compact_cts_device(self.ctx, d_cts, n, bits as c_int, d_out, hip_stream))
+    }
+
+    /// Knobs of the compact kernel (`omr_ctx_set_compact_grid`, `omr_ctx_set_compact_staging`; 0 =
+    /// default); the results do not depend on them.
+    pub fn set_compact_knobs(&self, workgroups: u32, max_ciphertexts: usize) -> Result<(), OmrError> {
+        check(unsafe { omr_ctx_set_compact_grid(self.ctx, workgroups as c_uint) })?;
+        check(unsafe { omr_ctx_set_compact_staging(self.ctx, max_ciphertexts) })
+    }
+
+    /// `encode_bitmap` on device buffers (`omr_encode_bitmap_device`), enqueued on `hip_stream`.
     ///
     /// # Safety
     /// `d_pv` must be device memory of `d` pertinency ciphertexts (16-byte aligned) and `d_out` of
@@ -834,6 +879,23 @@ impl DigestSession<'_> {
         check(unsafe { omr_digest_merge_bitmap(self.raw, cts.as_ptr()) })
     }
 
+    /// The digest at `bits` bits per coefficient (`omr_digest_read_compact`): the index and payload
+    /// ciphertexts, and the bitmap's when `bitmap` is set, `512 * bits` bytes each. The running digest is
+    /// not modified.
+    pub fn read_compact(&self, bits: i32, bitmap: bool) -> Result<CompactDigest, OmrError> {
+        let info = self.info()?;
+        let ctb = compact_ct_bytes(bits)?;
+        let mut indices = vec![0u8; info.index_ct as usize * ctb];
+        let mut payloads = vec![0u8; info.payload_ct as usize * ctb];
+        let mut bmp = vec![0u8; if bitmap { bitmap_ct_count(info.all_payloads_count)? * ctb } else { 0 }];
+        let p_bmp = if bitmap { bmp.as_mut_ptr() as *mut c_void } else { std::ptr::null_mut() };
+        check(unsafe {
+            omr_digest_read_compact(self.raw, bits as c_int, indices.as_mut_ptr() as *mut c_void,
+                                    payloads.as_mut_ptr() as *mut c_void, p_bmp)
+        })?;
+        Ok(CompactDigest { bits, indices, payloads, bitmap: bmp })
+    }
+
     pub fn info(&self) -> Result<OmrDigestInfo, OmrError> {
         let mut info = OmrDigestInfo::default();
         check(unsafe { omr_digest_get_info(self.raw, &mut info) })?;
@@ -845,6 +907,50 @@ impl Drop for DigestSession<'_> {
     fn drop(&mut self) {
         unsafe { omr_digest_destroy(self.raw) }
     }
+}
+
+/// A digest in compact form (`omr_digest_read_compact`): `512 * bits` bytes per ciphertext; `bitmap` is
+/// empty when it was not asked for.
+pub struct CompactDigest {
+    pub bits: i32,
+    pub indices: Vec<u8>,
+    pub payloads: Vec<u8>,
+    pub bitmap: Vec<u8>,
+}
+
+/// Bytes of one compact ciphertext, `512 * bits` (`omr_compact_ct_bytes`); `bits` in 16..=32.
+pub fn compact_ct_bytes(bits: i32) -> Result<usize, OmrError> {
+    let mut n = 0usize;
+    check(unsafe { omr_compact_ct_bytes(bits as c_int, &mut n) })?;
+    Ok(n)
+}
+
+/// Compact ciphertexts on the CPU (`omr_compact_cts_cpu`): `512 * bits` bytes per ciphertext.
+pub fn compact_cts_cpu(cts: &[NttRlwe], bits: i32, nthreads: i32) -> Result<Vec<u8>, OmrError> {
+    let flat = NttRlwe::flatten(cts);
+    let mut out = vec![0u8; cts.len() * compact_ct_bytes(bits)?];
+    check(unsafe { omr_compact_cts_cpu(flat.as_ptr(), cts.len(), bits as c_int, out.as_mut_ptr() as *mut c_void, nthreads) })?;
+    Ok(out)
+}
+
+/// Compact ciphertexts back to `NttRlwe` on the CPU (`omr_compact_expand_cpu`).
+pub fn compact_expand_cpu(packed: &[u8], bits: i32, nthreads: i32) -> Result<Vec<NttRlwe>, OmrError> {
+    let ctb = compact_ct_bytes(bits)?;
+    if packed.len() % ctb != 0 {
+        return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "512 * bits bytes per compact ciphertext".into() });
+    }
+    let n = packed.len() / ctb;
+    let mut out = vec![0u64; n * 2 * OMR_N2];
+    check(unsafe { omr_compact_expand_cpu(packed.as_ptr() as *const c_void, n, bits as c_int, out.as_mut_ptr(), nthreads) })?;
+    Ok(out.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect())
+}
+
+/// R(bits) for the pack's second-level key (`omr_compact_residual_bound`): decoding a compacted
+/// ciphertext is proven correct when its largest residual before compaction plus R is at most (q2 - 1) / 2.
+pub fn compact_residual_bound(secret: &SecretKeyPack, bits: i32) -> Result<u64, OmrError> {
+    let mut r = 0u64;
+    check(unsafe { omr_compact_residual_bound(secret.raw, bits as c_int, &mut r) })?;
+    Ok(r)
 }
 
 /// Bitmap ciphertexts of a board, `ceil(all / 16384)` (`omr_bitmap_ct_count`).
@@ -1007,6 +1113,33 @@ impl<'a> Auditor<'a> {
                           summary, nthreads)
         })?;
         Ok(Audit { records, decoded, summary: *summary })
+    }
+
+    /// Compact ciphertexts in host memory, expanded and audited on the device (`omr_audit_compact`):
+    /// the results of `audit` over their expansion, added into `summary`.
+    pub fn audit_compact(&self, packed: &[u8], bits: i32, summary: &mut OmrAuditSummary) -> Result<Audit, OmrError> {
+        let ctb = compact_ct_bytes(bits)?;
+        if packed.len() % ctb != 0 {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "512 * bits bytes per compact ciphertext".into() });
+        }
+        let n = packed.len() / ctb;
+        let mut records = vec![OmrCtAudit::default(); n];
+        let mut decoded = vec![0u16; n * OMR_N2];
+        check(unsafe {
+            omr_audit_compact(self.raw, packed.as_ptr() as *const c_void, n, bits as c_int, records.as_mut_ptr(),
+                              decoded.as_mut_ptr(), summary)
+        })?;
+        Ok(Audit { records, decoded, summary: *summary })
+    }
+
+    /// Device buffers of the auditor's GPU (`omr_compact_expand_device`): returns once enqueued.
+    ///
+    /// # Safety
+    /// `d_packed` must be device memory of `n * 512 * bits` bytes and `d_cts` of `n` ciphertexts, both
+    /// 16-byte aligned and valid until the stream has run the work.
+    pub unsafe fn expand_device(&self, d_packed: *const c_void, n: usize, bits: i32, d_cts: *mut u64,
+                                hip_stream: *mut c_void) -> Result<(), OmrError> {
+        check(omr_compact_expand_device(self.raw, d_packed, n, bits as c_int, d_cts, hip_stream))
     }
 
     /// Device buffers of the auditor's GPU (`omr_audit_device`): returns once enqueued on `hip_stream`.

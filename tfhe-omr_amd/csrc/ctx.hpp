@@ -5,6 +5,7 @@
 //   coalesce.hip  omr_detect's queue
 //   encode.hip    the encode kernels' launches and entry points
 //   digest.hip    the digest session over detect and encode
+//   compact.hip   compact ciphertexts: both kernels' launches (lent through compact.hpp), the context's entry points
 // One rule for kernels: a non-template __global__ function lives in a header that exactly one of these
 // includes (or in the .hip itself); a second includer would define its host stub twice and the link
 // fails. Headers that several units share (kernels.hpp, device_*.hpp, fft1024.hpp, exactness.hpp,
@@ -117,6 +118,15 @@ struct omr_ctx {
     omr_detect_timing host{};
     bool host_valid = false;
   } tm;
+
+  // Compact ciphertexts (compact.hip): omr_compact_cts's staging on the context's own stream, grown on
+  // demand, and the two knobs. The kernel needs the inverse twiddles of `tab` and nothing else.
+  struct Compact {
+    omr::DevBuf<uint64_t> stage;   // one piece of ciphertexts
+    omr::DevBuf<uint32_t> packed;  // its compact form
+    unsigned grid = 0;             // workgroups; 0: six per compute unit (omr_ctx_set_compact_grid)
+    size_t staging = 0;            // ciphertexts per piece; 0: 2,048 (omr_ctx_set_compact_staging)
+  } cp;
 
   // omr_detect's coalescer (coalesce.hip): everything here is guarded by its own mutex `mu`, never
   // by the context's. A leader takes every queued request, runs them as one detect and wakes the callers.

@@ -5,6 +5,7 @@
 // chunk partials added to the running digest mod q2. The digest is an exact sum mod q2 of
 // per-message terms, so any partition of the board into updates gives the same bits. A session whose
 // bitmap is enabled (omr_digest_enable_bitmap) folds each piece into the bitmap digest as well.
+// omr_digest_read_compact hands the digest out in compact form (compact.hpp) and leaves it as it is.
 //
 // The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
 // context's detect / encode scratch under the context mutex (ctx.hpp), like any other call.
@@ -14,6 +15,7 @@
 #include <new>
 #include <vector>
 
+#include "compact.hpp"
 #include "ctx.hpp"
 #include "digest_ranges.hpp"
 
@@ -30,6 +32,7 @@ struct omr_digest {
   DevBuf<uint64_t> pv;           // pertinency ciphertexts of one piece, grown lazily
   DevBuf<uint64_t> merge_stage;  // omr_digest_merge's and omr_digest_merge_bitmap's upload
   DevBuf<uint64_t> bitmap;       // [n_bmp][2][N2], canonical; empty until omr_digest_enable_bitmap
+  DevBuf<uint32_t> compact;      // omr_digest_read_compact's packed digest, then bitmap (grown on demand)
   uint32_t n_bmp = 0;            // omr_bitmap_ct_count(all) once the bitmap is enabled, else 0
   bool started = false;          // an update or a merge has been accepted: too late to enable the bitmap
   DevBuf<uint16_t> s_clue_a, s_clue_b, s_payloads;  // host updates' staging, grown together
@@ -204,6 +207,42 @@ extern "C" omr_status omr_digest_read(omr_digest *dg, uint64_t *idx_cts, uint64_
   const size_t ni = (size_t)dg->n_idx() * 2 * N2, np = (size_t)dg->n_pay() * 2 * N2;
   if (idx_cts) HIP_TRY(hipMemcpy(idx_cts, dg->digest, ni * sizeof(uint64_t), hipMemcpyDeviceToHost));
   if (pay_cts) HIP_TRY(hipMemcpy(pay_cts, dg->digest + ni, np * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_read_compact(omr_digest *dg, int bits, void *idx_packed, void *pay_packed,
+                                              void *bitmap_packed) {
+  if (!dg) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read_compact: NULL session");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  if (dg->poisoned) return poisoned_error("omr_digest_read_compact");
+  if (!compact_bits_ok(bits))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read_compact: bits must be in [16, 32]");
+  if (bitmap_packed && !dg->n_bmp)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_read_compact: the bitmap is not enabled");
+  omr_ctx *c = dg->ctx;
+  std::lock_guard<std::mutex> cl(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(dg->st));
+  omr_status s;
+  if ((s = take_handoff_error(c)) != OMR_OK) {
+    dg->poisoned = true;
+    return s;
+  }
+  // the stream is idle here, so the packed buffer may grow; the running digest is only read
+  const size_t ctb = compact_ct_bytes(bits), ni = dg->n_idx(), np = dg->n_pay(), nd = ni + np;
+  const size_t nb = bitmap_packed ? dg->n_bmp : 0;
+  const bool want_digest = idx_packed || pay_packed;
+  if (!want_digest && !nb) return OMR_OK;
+  HIP_TRY(dg->compact.reserve((nd + nb) * ctb / sizeof(uint32_t)));
+  uint8_t *d_digest = (uint8_t *)dg->compact.get(), *d_bitmap = d_digest + nd * ctb;
+  if (want_digest)
+    OMR_TRY(launch_compact(dg->digest, nd, bits, c->tab.tb.itw2, compact_grid(c->cp.grid, c->ho.num_cu, nd), d_digest, dg->st));
+  if (nb)
+    OMR_TRY(launch_compact(dg->bitmap, nb, bits, c->tab.tb.itw2, compact_grid(c->cp.grid, c->ho.num_cu, nb), d_bitmap, dg->st));
+  HIP_TRY(hipStreamSynchronize(dg->st));
+  if (idx_packed) HIP_TRY(hipMemcpy(idx_packed, d_digest, ni * ctb, hipMemcpyDeviceToHost));
+  if (pay_packed) HIP_TRY(hipMemcpy(pay_packed, d_digest + ni * ctb, np * ctb, hipMemcpyDeviceToHost));
+  if (nb) HIP_TRY(hipMemcpy(bitmap_packed, d_bitmap, nb * ctb, hipMemcpyDeviceToHost));
   return OMR_OK;
 }
 

@@ -5,7 +5,7 @@
 // indices and their payloads come back.
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
-//           [--host-only]
+//           [--compact BITS] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -20,6 +20,11 @@
 // mask seed, 146 MiB instead of 363) and builds the detector through omr_ctx_create_seeded, which expands
 // it on the device. With --host-only the key is expanded on the host (omr_expand_detection_key) and its
 // masks are checked against omr_key_masks.
+// --compact BITS sends the digest in compact form (include/omr_gpu.h, "Compact ciphertexts"): the detector
+// compacts it on the GPU to BITS bits per coefficient (omr_compact_cts, or the session's
+// omr_digest_read_compact), the recipient expands it (omr_compact_expand_cpu) and retrieves from that. Both
+// sizes, R(BITS) for the recipient's key and the measured residual increase are printed; an increase above R
+// or a decoded value that changed fails the run.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -62,6 +67,7 @@ int main(int argc, char **argv) {
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
   bool audit = false, bitmap = false, seeded = false;
+  int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if ((a == "-p" || a == "--payload-count") && i + 1 < argc) D = std::max<size_t>(1, std::stoull(argv[++i]));
@@ -71,10 +77,11 @@ int main(int argc, char **argv) {
     else if (a == "--audit") audit = true;
     else if (a == "--bitmap") bitmap = true;
     else if (a == "--seeded") seeded = true;
+    else if (a == "--compact" && i + 1 < argc) compact_bits = std::atoi(argv[++i]);
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--seeded] [--host-only]\n",
+                   "[--seeded] [--compact BITS] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -196,6 +203,9 @@ int main(int argc, char **argv) {
   int audit_fails = 0;
   omr_audit_summary pv_sum{}, dg_sum{};
   std::vector<uint64_t> idx_ct((size_t)n_idx * 2 * N2), pay_ct((size_t)n_pay * 2 * N2), bmp_ct((size_t)n_bmp * 2 * N2);
+  size_t ctb = 0;  // bytes of one compact ciphertext
+  if (compact_bits) CHECK(omr_compact_ct_bytes(compact_bits, &ctb));
+  std::vector<uint8_t> idx_pk(n_idx * ctb), pay_pk(n_pay * ctb), bmp_pk(n_bmp * ctb);
   if (session_piece) {
     // the same flow inside the library, piece by piece (omr_digest_*): detect + both encoders
     t = clk::now();
@@ -208,6 +218,7 @@ int main(int argc, char **argv) {
     }
     CHECK(omr_digest_read(dg, idx_ct.data(), pay_ct.data()));
     if (bitmap) CHECK(omr_digest_read_bitmap(dg, bmp_ct.data()));
+    if (compact_bits) CHECK(omr_digest_read_compact(dg, compact_bits, idx_pk.data(), pay_pk.data(), bitmap ? bmp_pk.data() : nullptr));
     omr_digest_info info;
     CHECK(omr_digest_get_info(dg, &info));
     omr_digest_destroy(dg);
@@ -254,6 +265,45 @@ int main(int argc, char **argv) {
       CHECK(omr_encode_bitmap(ctx, pv.data(), D, 0, D, bmp_ct.data()));
       std::printf("encode bitmap time: %.3f s\n", secs(t));
     }
+    if (compact_bits) {
+      CHECK(omr_compact_cts(ctx, idx_ct.data(), n_idx, compact_bits, idx_pk.data()));
+      CHECK(omr_compact_cts(ctx, pay_ct.data(), n_pay, compact_bits, pay_pk.data()));
+      CHECK(omr_compact_cts(ctx, bmp_ct.data(), n_bmp, compact_bits, bmp_pk.data()));
+    }
+  }
+
+  int compact_fails = 0;
+  if (compact_bits) {
+    // the recipient's side: expand what arrived and retrieve from that; the full digest is kept only to
+    // measure what compaction cost
+    uint64_t R = 0, before = 0, after = 0, grow = 0;
+    CHECK(omr_compact_residual_bound(pa, compact_bits, &R));
+    struct Part {
+      std::vector<uint64_t> *full;
+      std::vector<uint8_t> *packed;
+      uint32_t n;
+    } parts[3] = {{&idx_ct, &idx_pk, n_idx}, {&pay_ct, &pay_pk, n_pay}, {&bmp_ct, &bmp_pk, n_bmp}};
+    for (Part &pt : parts) {
+      if (!pt.n) continue;
+      std::vector<omr_ct_audit> r0(pt.n), r1(pt.n);
+      std::vector<uint16_t> d0((size_t)pt.n * N2), d1((size_t)pt.n * N2);
+      CHECK(omr_audit_cpu(pa, pt.full->data(), pt.n, r0.data(), d0.data(), nullptr, 0));
+      CHECK(omr_compact_expand_cpu(pt.packed->data(), pt.n, compact_bits, pt.full->data(), 0));
+      CHECK(omr_audit_cpu(pa, pt.full->data(), pt.n, r1.data(), d1.data(), nullptr, 0));
+      if (d0 != d1) ++compact_fails;
+      for (uint32_t c = 0; c < pt.n; ++c) {
+        before = std::max(before, r0[c].max_abs_residual);
+        after = std::max(after, r1[c].max_abs_residual);
+        if (r1[c].max_abs_residual > r0[c].max_abs_residual) grow = std::max(grow, r1[c].max_abs_residual - r0[c].max_abs_residual);
+      }
+    }
+    if (grow > R) ++compact_fails;
+    const size_t n_all = (size_t)n_idx + n_pay + n_bmp;
+    std::printf("compact digest: %zu ciphertexts at %d bits, %zu bytes instead of %zu; R/q2 %.4e, max |r|/q2 %.3e -> %.3e, "
+                "largest increase %.3e%s\n",
+                n_all, compact_bits, n_all * ctb, n_all * 2 * N2 * 8, (double)R / (double)OMR_Q2,
+                (double)before / (double)OMR_Q2, (double)after / (double)OMR_Q2, (double)grow / (double)OMR_Q2,
+                compact_fails ? " -- FAILED" : "");
   }
 
   if (audit) {
@@ -291,7 +341,7 @@ int main(int argc, char **argv) {
                               solved.data()));
   std::printf("decode time: %.3f s\n", secs(t));
 
-  int fails = (found == pert ? 0 : 1) + audit_fails;
+  int fails = (found == pert ? 0 : 1) + audit_fails + compact_fails;
   if (fails) std::printf("Fail: %zu indices recovered, %zu pertinent\n", found.size(), pert.size());
   for (size_t k = 0; k < found.size() && !fails; ++k)
     if (!std::equal(&solved[k * PAYLOAD], &solved[(k + 1) * PAYLOAD], &payloads[found[k] * PAYLOAD])) {

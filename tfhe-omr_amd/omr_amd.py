@@ -176,6 +176,18 @@ EXPORTS = {
                                    C.c_void_p]),
     "omr_audit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "omr_audit_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "omr_compact_ct_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "omr_compact_residual_bound": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "omr_compact_cts_cpu": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int]),
+    "omr_compact_expand_cpu": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int]),
+    "omr_compact_cts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "omr_compact_cts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "omr_ctx_set_compact_grid": (C.c_int, [C.c_void_p, C.c_uint]),
+    "omr_ctx_set_compact_staging": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "omr_compact_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "omr_audit_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "omr_digest_read_compact": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "omr_second_level": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_blind_rotate_level2": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_ntt": (C.c_int, [C.c_int, C.c_int, _u64p, C.c_size_t, C.c_int]),
@@ -558,6 +570,51 @@ class Retriever:
         return indices, self.decode_combined_payloads_and_solve(pay_cts, weights, indices)
 
 
+# ---- compact ciphertexts (include/omr_gpu.h, "Compact ciphertexts") ---------------------------
+COMPACT_MIN_BITS, COMPACT_MAX_BITS = 16, 32
+
+
+def compact_ct_bytes(bits: int) -> int:
+    """omr_compact_ct_bytes: 512 * bits bytes per compact ciphertext."""
+    n = C.c_size_t()
+    _check(lib().omr_compact_ct_bytes(bits, C.byref(n)), "omr_compact_ct_bytes")
+    return n.value
+
+
+def compact_residual_bound(secret: "SecretKeyPack", bits: int) -> int:
+    """omr_compact_residual_bound: R(bits) for the pack's s2, in the auditor's residual units."""
+    r = C.c_uint64()
+    _check(lib().omr_compact_residual_bound(secret._h, bits, C.byref(r)), "omr_compact_residual_bound")
+    return r.value
+
+
+def _packed(packed, bits: int) -> np.ndarray:
+    """Compact ciphertexts as u8 [n][512 * bits]."""
+    p = np.ascontiguousarray(packed, dtype=np.uint8)
+    ctb = compact_ct_bytes(bits)
+    if p.size % ctb:
+        raise OmrError(f"compact ciphertexts at {bits} bits must be a multiple of {ctb} bytes")
+    return p.reshape(-1, ctb)
+
+
+def compact_cts_cpu(cts, bits: int, nthreads: int = 0) -> np.ndarray:
+    """omr_compact_cts_cpu: NttRlweCiphertexts u64 [n][2][2048] -> u8 [n][512 * bits], on the CPU."""
+    cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, N2)
+    out = np.empty((cts.shape[0], compact_ct_bytes(bits)), np.uint8)
+    _check(lib().omr_compact_cts_cpu(cts.ctypes.data, cts.shape[0], bits, out.ctypes.data, nthreads),
+           "omr_compact_cts_cpu")
+    return out
+
+
+def compact_expand_cpu(packed, bits: int, nthreads: int = 0) -> np.ndarray:
+    """omr_compact_expand_cpu: u8 [n][512 * bits] -> NttRlweCiphertexts u64 [n][2][2048], on the CPU."""
+    p = _packed(packed, bits)
+    out = np.empty((p.shape[0], 2, N2), np.uint64)
+    _check(lib().omr_compact_expand_cpu(p.ctypes.data, p.shape[0], bits, out.ctypes.data, nthreads),
+           "omr_compact_expand_cpu")
+    return out
+
+
 def _summary_dict(t: "_AuditSummary") -> dict:
     d = {n: int(getattr(t, n)) for n in ("ciphertexts", "zero", "one_hot", "other", "max_abs_residual")}
     d["residual_bits"] = np.array(t.residual_bits[:], dtype=np.uint64)
@@ -626,6 +683,24 @@ class Auditor:
         on `stream`; the caller synchronises."""
         _check(lib().omr_audit_device(self._h, d_cts, n, d_records or None, d_decoded or None, d_summary or None,
                                       stream or None), "omr_audit_device")
+
+    def audit_compact(self, packed, bits: int):
+        """Compact ciphertexts u8 [n][512 * bits] in host memory through the device (omr_audit_compact):
+        expanded and audited there; (records, decoded, summary) as from audit() of their expansion."""
+        p = _packed(packed, bits)
+        n = p.shape[0]
+        records = np.zeros(n, AUDIT_RECORD)
+        decoded = np.zeros((n, N2), np.uint16)
+        t = _AuditSummary()
+        _check(lib().omr_audit_compact(self._h, p.ctypes.data, n, bits, records.ctypes.data, decoded.ctypes.data,
+                                       C.addressof(t)), "omr_audit_compact")
+        return records, decoded, _summary_dict(t)
+
+    def expand_device(self, d_packed: int, n: int, bits: int, d_cts: int, stream: int = 0) -> None:
+        """Device pointers (omr_compact_expand_device): n compact ciphertexts -> u64 [n][2][2048]. Enqueued
+        on `stream`; the caller synchronises."""
+        _check(lib().omr_compact_expand_device(self._h, d_packed or None, n, bits, d_cts or None, stream or None),
+               "omr_compact_expand_device")
 
     @staticmethod
     def summary_from_bytes(buf) -> dict:
@@ -878,6 +953,25 @@ class Detector:
                                                 d_weights, n_ct, per_ct, d_out, stream or None),
                "omr_encode_payloads_device")
 
+    # compact ciphertexts (include/omr_gpu.h, "Compact ciphertexts"): the server side
+    def compact_cts(self, cts, bits: int) -> np.ndarray:
+        """omr_compact_cts: host NttRlweCiphertexts u64 [n][2][2048] -> u8 [n][512 * bits] through the device."""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, N2)
+        out = np.empty((cts.shape[0], compact_ct_bytes(bits)), np.uint8)
+        _check(lib().omr_compact_cts(self._h, cts.ctypes.data, cts.shape[0], bits, out.ctypes.data), "omr_compact_cts")
+        return out
+
+    def compact_cts_device(self, d_cts: int, n: int, bits: int, d_out: int, stream: int = 0) -> None:
+        """omr_compact_cts_device: device pointers, enqueued on `stream`; the caller synchronises."""
+        _check(lib().omr_compact_cts_device(self._h, d_cts or None, n, bits, d_out or None, stream or None),
+               "omr_compact_cts_device")
+
+    def set_compact_grid(self, workgroups: int = 0):
+        _check(lib().omr_ctx_set_compact_grid(self._h, workgroups), "omr_ctx_set_compact_grid")
+
+    def set_compact_staging(self, max_ciphertexts: int = 0):
+        _check(lib().omr_ctx_set_compact_staging(self._h, max_ciphertexts), "omr_ctx_set_compact_staging")
+
     def digest_session(self, all_payloads_count: int, pertinent_count: int, index_seed: int, weight_seed: bytes,
                        stream: int = 0) -> "DigestSession":
         """A digest session on this detector (omr_digest_begin): detect + encode a board piece by
@@ -979,6 +1073,18 @@ class DigestSession:
         pay = np.empty((self._info["payload_ct"], 2, N2), np.uint64)
         _check(lib().omr_digest_read(self._h, idx.ctypes.data, pay.ctypes.data), "omr_digest_read")
         return idx, pay
+
+    def read_compact(self, bits: int, bitmap: bool = False):
+        """omr_digest_read_compact: the digest at `bits` bits per coefficient, (idx u8 [index_ct][512 * bits],
+        pay u8 [payload_ct][512 * bits]) and, with bitmap=True, the bitmap digest the same way as a third
+        array. The running digest is not modified."""
+        ctb = compact_ct_bytes(bits)
+        idx = np.empty((self._info["index_ct"], ctb), np.uint8)
+        pay = np.empty((self._info["payload_ct"], ctb), np.uint8)
+        bmp = np.empty((bitmap_ct_count(self._info["all_payloads_count"]), ctb), np.uint8) if bitmap else None
+        _check(lib().omr_digest_read_compact(self._h, bits, idx.ctypes.data, pay.ctypes.data,
+                                             bmp.ctypes.data if bitmap else None), "omr_digest_read_compact")
+        return (idx, pay, bmp) if bitmap else (idx, pay)
 
     def enable_bitmap(self) -> None:
         """omr_digest_enable_bitmap: also keep the board's bitmap digest; before the first update or merge."""
