@@ -675,6 +675,23 @@ omr_status omr_second_level(omr_ctx *ctx, const uint32_t *lwe_int, size_t n, uin
 /* Level-2 blind rotation only (no trace): out u64 [n][2][2048] coefficient domain. */
 omr_status omr_blind_rotate_level2(omr_ctx *ctx, const uint32_t *lwe_int, size_t n,
                                    uint64_t *out);
+/* Test entries: the blind rotations from a caller-supplied initial accumulator acc0, u64 [n][2][N]
+ * (level 1: N = 1024 mod q1; level 2: N = 2048 mod q2) of canonical residues in the coefficient
+ * domain, in the layout of the matching entry's output. It replaces (0, X^-b * LUT); the LWE body
+ * (lwe_b, which may then be NULL; lwe_int[670]) is ignored. With a rotation amount a = N,
+ * (X^a - 1) * ACC = -2 ACC, so every decomposition input T is reachable as ACC = -T * 2^-1 mod q,
+ * and an LWE with one nonzero a_i runs exactly one CMUX step on that step's key rows. acc0 == NULL
+ * behaves exactly as the entry without _from. A word >= q is OMR_ERR_INVALID_ARGUMENT, checked on
+ * the host before anything is enqueued. The same kernel selection, guard and fallback as the
+ * matching entry, on those kernels' _from instantiations. */
+omr_status omr_blind_rotate_level1_from(omr_ctx *ctx, const uint16_t *lwe_a, const uint16_t *lwe_b,
+                                        size_t n, const uint64_t *acc0, uint64_t *out);
+omr_status omr_blind_rotate_level2_from(omr_ctx *ctx, const uint32_t *lwe_int, size_t n,
+                                        const uint64_t *acc0, uint64_t *out);
+/* Test entry: the homomorphic trace alone (what omr_second_level runs after its rotation, with the
+ * same kernel selection, guard and fallback) on n coefficient-domain RLWEs, rlwe u64 [n][2][2048]
+ * canonical (a word >= q2 is OMR_ERR_INVALID_ARGUMENT): out u64 [n][2][2048], NTT domain. */
+omr_status omr_trace(omr_ctx *ctx, const uint64_t *rlwe, size_t n, uint64_t *out);
 /* Forward / inverse NTT of n polynomials (level 1: N=1024 mod q1, level 2: N=2048 mod q2). */
 omr_status omr_ntt(int level, int inverse, uint64_t *polys, size_t n, int device);
 

@@ -358,16 +358,21 @@ static void ext_product(int level, const uint64_t *ca, const uint64_t *cb, const
   free(dig);
 }
 
-/* lwe_a values are already mod 2N. out: (a, b) coefficient domain, 2N u64. */
+/* lwe_a values are already mod 2N. out: (a, b) coefficient domain, 2N u64. acc0 (optional): the
+ * initial accumulator (a, b), canonical, instead of (0, X^{-b} * LUT); lwe_b is then unused. */
 static void blind_rotate(int level, const uint64_t *lut, const uint32_t *lwe_a, uint32_t lwe_b,
-                         int n, const uint64_t *bsk, uint64_t *out) {
+                         int n, const uint64_t *bsk, const uint64_t *acc0, uint64_t *out) {
   const ntt_tab *t = &g_tab[level];
   const int N = t->N;
   const size_t ggsw_sz = (size_t)2 * g_basis[level].d * 2 * N;
   uint64_t *acc_a = out, *acc_b = out + N;
   uint64_t *ta = malloc(sizeof(uint64_t) * N * 4), *tb = ta + N, *ra = tb + N, *rb = ra + N;
-  memset(acc_a, 0, sizeof(uint64_t) * N);
-  mul_monomial(t, lut, (2u * N - lwe_b % (2u * N)) % (2u * N), acc_b); /* X^{-b} * LUT */
+  if (acc0) {
+    memcpy(out, acc0, sizeof(uint64_t) * 2 * N);
+  } else {
+    memset(acc_a, 0, sizeof(uint64_t) * N);
+    mul_monomial(t, lut, (2u * N - lwe_b % (2u * N)) % (2u * N), acc_b); /* X^{-b} * LUT */
+  }
   for (int i = 0; i < n; ++i) {
     const uint32_t ai = lwe_a[i] % (2u * N);
     if (ai == 0) continue; /* (X^0 - 1) * ACC = 0: the external product is exactly 0 */
@@ -412,7 +417,13 @@ uint32_t oref_clue_phase(const uint16_t *clue_a, const uint16_t *clue_b, int i, 
 void oref_br1(const oref_ctx *ctx, const uint16_t *lwe_a, uint16_t lwe_b, uint64_t *rlwe_out) {
   uint32_t a[OREF_N0];
   for (int j = 0; j < OREF_N0; ++j) a[j] = lwe_a[j]; /* q0 == 2*N1: no modulus switch (:519-529) */
-  blind_rotate(1, ctx->lut1, a, lwe_b, OREF_N0, ctx->bsk1, rlwe_out);
+  blind_rotate(1, ctx->lut1, a, lwe_b, OREF_N0, ctx->bsk1, NULL, rlwe_out);
+}
+/* oref_br1 from a supplied initial accumulator acc0 (2 * N1 canonical residues: a then b) */
+void oref_br1_from(const oref_ctx *ctx, const uint16_t *lwe_a, const uint64_t *acc0, uint64_t *rlwe_out) {
+  uint32_t a[OREF_N0];
+  for (int j = 0; j < OREF_N0; ++j) a[j] = lwe_a[j];
+  blind_rotate(1, ctx->lut1, a, 0, OREF_N0, ctx->bsk1, acc0, rlwe_out);
 }
 
 /* first_level_bootstrapping, detector.rs:533-597 */
@@ -452,7 +463,11 @@ void oref_first_level(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_
 
 /* second_level_bootstrapping, detector.rs:599-624 (4096 == 2*N2: no modulus switch) */
 void oref_br2(const oref_ctx *ctx, const uint32_t *lwe_int, uint64_t *rlwe_out) {
-  blind_rotate(2, ctx->lut2, lwe_int, lwe_int[OREF_NI], OREF_NI, ctx->bsk2, rlwe_out);
+  blind_rotate(2, ctx->lut2, lwe_int, lwe_int[OREF_NI], OREF_NI, ctx->bsk2, NULL, rlwe_out);
+}
+/* oref_br2 from a supplied initial accumulator acc0 (2 * N2 canonical residues: a then b) */
+void oref_br2_from(const oref_ctx *ctx, const uint32_t *lwe_int, const uint64_t *acc0, uint64_t *rlwe_out) {
+  blind_rotate(2, ctx->lut2, lwe_int, lwe_int[OREF_NI], OREF_NI, ctx->bsk2, acc0, rlwe_out);
 }
 
 /* hom_trace, detector.rs:626-639 */

@@ -98,6 +98,10 @@ void oref_br1(const oref_ctx *ctx, const uint16_t *lwe_a, uint16_t lwe_b, uint64
 void oref_first_level(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,
                       uint32_t *lwe_int /* 671: a[670], b; mod 4096 */);
 void oref_br2(const oref_ctx *ctx, const uint32_t *lwe_int, uint64_t *rlwe_out);
+/* The blind rotations from a supplied initial accumulator acc0 (u64 [2][N], canonical, coefficient
+ * domain: the outputs' layout) instead of (0, X^{-b} * LUT); the LWE body is unused. */
+void oref_br1_from(const oref_ctx *ctx, const uint16_t *lwe_a, const uint64_t *acc0, uint64_t *rlwe_out);
+void oref_br2_from(const oref_ctx *ctx, const uint32_t *lwe_int, const uint64_t *acc0, uint64_t *rlwe_out);
 void oref_trace(const oref_ctx *ctx, const uint64_t *rlwe_in, uint64_t *ntt_out);
 void oref_detect(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,
                  uint64_t *out /* 2*2048 NTT domain: a then b */);

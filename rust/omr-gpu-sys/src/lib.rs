@@ -313,6 +313,11 @@ pub mod ffi {
         pub fn omr_fft1_mul(ctx: *mut OmrCtx, a: *const u32, k: *const u32, n: usize, out: *mut u64) -> OmrStatus;
         pub fn omr_second_level(ctx: *mut OmrCtx, lwe_int: *const u32, n: usize, out: *mut u64) -> OmrStatus;
         pub fn omr_blind_rotate_level2(ctx: *mut OmrCtx, lwe_int: *const u32, n: usize, out: *mut u64) -> OmrStatus;
+        pub fn omr_blind_rotate_level1_from(ctx: *mut OmrCtx, lwe_a: *const u16, lwe_b: *const u16, n: usize,
+                                            acc0: *const u64, out: *mut u64) -> OmrStatus;
+        pub fn omr_blind_rotate_level2_from(ctx: *mut OmrCtx, lwe_int: *const u32, n: usize, acc0: *const u64,
+                                            out: *mut u64) -> OmrStatus;
+        pub fn omr_trace(ctx: *mut OmrCtx, rlwe: *const u64, n: usize, out: *mut u64) -> OmrStatus;
         pub fn omr_ntt(level: c_int, inverse: c_int, polys: *mut u64, n: usize, device: c_int) -> OmrStatus;
     }
 }

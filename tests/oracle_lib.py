@@ -47,6 +47,8 @@ def lib():
         "oref_br1": (None, [C.c_void_p, _u16p, C.c_uint16, _u64p]),
         "oref_first_level": (None, [C.c_void_p, _u16p, _u16p, _u32p]),
         "oref_br2": (None, [C.c_void_p, _u32p, _u64p]),
+        "oref_br1_from": (None, [C.c_void_p, _u16p, _u64p, _u64p]),
+        "oref_br2_from": (None, [C.c_void_p, _u32p, _u64p, _u64p]),
         "oref_trace": (None, [C.c_void_p, _u64p, _u64p]),
         "oref_detect": (None, [C.c_void_p, _u16p, _u16p, _u64p]),
         "oref_detect_batch": (None, [C.c_void_p, _u16p, _u16p, C.c_size_t, _u64p, C.c_int]),
@@ -102,6 +104,20 @@ class OracleDetector:
     def br2(self, lwe_int):
         out = np.zeros(2 * 2048, dtype=np.uint64)
         lib().oref_br2(self._h, np.ascontiguousarray(lwe_int, dtype=np.uint32), out)
+        return out.reshape(2, 2048)
+
+    def br1_from(self, lwe_a, acc0):
+        """br1 from the initial accumulator acc0 (u64 [2][1024], canonical); the LWE body is unused."""
+        out = np.zeros(2 * 1024, dtype=np.uint64)
+        lib().oref_br1_from(self._h, np.ascontiguousarray(lwe_a, dtype=np.uint16),
+                            np.ascontiguousarray(acc0, dtype=np.uint64).reshape(-1), out)
+        return out.reshape(2, 1024)
+
+    def br2_from(self, lwe_int, acc0):
+        """br2 from the initial accumulator acc0 (u64 [2][2048], canonical); lwe_int[670] is unused."""
+        out = np.zeros(2 * 2048, dtype=np.uint64)
+        lib().oref_br2_from(self._h, np.ascontiguousarray(lwe_int, dtype=np.uint32),
+                            np.ascontiguousarray(acc0, dtype=np.uint64).reshape(-1), out)
         return out.reshape(2, 2048)
 
     def trace(self, rlwe):

@@ -159,12 +159,15 @@ constexpr size_t BR1_LDS_XCH = 0, BR1_LDS_TWS = BR1_LDS_XCH + (size_t)BR1F_WPG *
                  BR1_LDS_KBUF = BR1_LDS_LA + (size_t)BR1F_WPG * N0 * sizeof(uint16_t),
                  BR1_LDS_BYTES = BR1_LDS_KBUF + 2 * (size_t)KROW_SLOTS * sizeof(double2);
 
-template <bool G>
+// FROM (the test entry omr_blind_rotate_level1_from): the initial accumulator is acc0's rotation
+// instead; separate kernels, so that the production kernels' code does not move.
+template <bool G, bool FROM = false>
 __device__ __forceinline__ void br1f_body(
     const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
     const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
     const double2 *__restrict__ bskf, DeviceTables tb, uint32_t *__restrict__ ext,
-    uint64_t *__restrict__ rlwe_out, int mode, size_t nrot, unsigned long long *margin, char *pool, size_t item) {
+    uint64_t *__restrict__ rlwe_out, int mode, size_t nrot, unsigned long long *margin, char *pool, size_t item,
+    const uint64_t *__restrict__ acc0 = nullptr) {
   constexpr int NF = Fft512::N, W = BR1F_WPG;
   static_assert(16 % W == 0, "LDS key staging: W divides the row's 16 one-KiB pieces");
   static_assert(Fft512::BUF * sizeof(double2) == 8192, "one 8 KB buffer per wave");
@@ -200,8 +203,13 @@ __device__ __forceinline__ void br1f_body(
   uint32_t ac[2][16];  // Lvl1Off: ac + OFF
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    ac[0][i] = Lvl1Off::enc(0);
-    ac[1][i] = Lvl1Off::enc((int)canon_small<Mod<1>>(rot_read<N1>(tb.lut1, acc_coef(lane, i), r0)));
+    if constexpr (FROM) {
+      ac[0][i] = Lvl1Off::enc(lvl1_acc_from(acc0, gi, 0, acc_coef(lane, i)));
+      ac[1][i] = Lvl1Off::enc(lvl1_acc_from(acc0, gi, 1, acc_coef(lane, i)));
+    } else {
+      ac[0][i] = Lvl1Off::enc(0);
+      ac[1][i] = Lvl1Off::enc((int)canon_small<Mod<1>>(rot_read<N1>(tb.lut1, acc_coef(lane, i), r0)));
+    }
   }
   for (int j = threadIdx.x; j < NF; j += 64 * W) tws[j] = tb.fft1[j];
   __syncthreads();
@@ -257,6 +265,25 @@ __global__ __launch_bounds__(64 * BR1F_WPG, 2) void br1f_guard_kernel(
     uint64_t *__restrict__ rlwe_out, int mode, size_t nrot, unsigned long long *margin) {
   __shared__ __attribute__((aligned(8192))) char pool[BR1_LDS_BYTES];
   br1f_body<true>(clue_a, clue_b, lwe_a, lwe_b, bskf, tb, ext, rlwe_out, mode, nrot, margin, pool, blockIdx.x);
+}
+__global__ __launch_bounds__(64 * BR1F_WPG, 2) void br1f_from_kernel(
+    const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
+    const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
+    const double2 *__restrict__ bskf, DeviceTables tb, uint32_t *__restrict__ ext,
+    uint64_t *__restrict__ rlwe_out, int mode, size_t nrot, const uint64_t *__restrict__ acc0) {
+  __shared__ __attribute__((aligned(8192))) char pool[BR1_LDS_BYTES];
+  br1f_body<false, true>(clue_a, clue_b, lwe_a, lwe_b, bskf, tb, ext, rlwe_out, mode, nrot, nullptr, pool,
+                         blockIdx.x, acc0);
+}
+__global__ __launch_bounds__(64 * BR1F_WPG, 2) void br1f_guard_from_kernel(
+    const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
+    const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
+    const double2 *__restrict__ bskf, DeviceTables tb, uint32_t *__restrict__ ext,
+    uint64_t *__restrict__ rlwe_out, int mode, size_t nrot, unsigned long long *margin,
+    const uint64_t *__restrict__ acc0) {
+  __shared__ __attribute__((aligned(8192))) char pool[BR1_LDS_BYTES];
+  br1f_body<true, true>(clue_a, clue_b, lwe_a, lwe_b, bskf, tb, ext, rlwe_out, mode, nrot, margin, pool, blockIdx.x,
+                        acc0);
 }
 
 // Test entry (omr_fft1_mul): out = a * k mod (X^1024 + 1, q1) through the level-1 FFT path,

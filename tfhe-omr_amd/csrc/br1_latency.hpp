@@ -36,12 +36,14 @@ namespace omr {
 // as in br1f_kernel, and the rounded FFT product is exact in either order (device_fft.hpp).
 constexpr int BR1L_WAVES = 2 * D1;
 
-template <bool G>
+// FROM: the initial accumulator is acc0's rotation instead (br1f_body's FROM).
+template <bool G, bool FROM = false>
 __device__ __forceinline__ void br1l_body(
     const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
     const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
     const double2 *__restrict__ bskl, DeviceTables tb, uint32_t *__restrict__ ext_out,
-    uint64_t *__restrict__ rlwe_out, int mode, unsigned long long *margin) {
+    uint64_t *__restrict__ rlwe_out, int mode, unsigned long long *margin,
+    const uint64_t *__restrict__ acc0 = nullptr) {
   using F = Fft512;
   constexpr int NF = F::N, W = BR1L_WAVES;
   static_assert(W == 8 && NF == 8 * 64, "one wave per GGSW row and per register slot");
@@ -61,7 +63,12 @@ __device__ __forceinline__ void br1l_body(
   // H - ac'' doubling as the digit operand; level1_common.hpp, tests/test_lvl1_offset_model.py)
   uint32_t ac[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) ac[i] = Lvl1Off::enc(wave == 1 ? (int)lvl1_acc_init(tb, b, acc_coef(lane, i)) : 0);
+  for (int i = 0; i < 16; ++i) {
+    if constexpr (FROM)
+      ac[i] = Lvl1Off::enc(wave < 2 ? lvl1_acc_from(acc0, g, wave, acc_coef(lane, i)) : 0);
+    else
+      ac[i] = Lvl1Off::enc(wave == 1 ? (int)lvl1_acc_init(tb, b, acc_coef(lane, i)) : 0);
+  }
   if (wave < 2) lvl1_stage_ext(ext[wave], ac, lane);
   for (int j = threadIdx.x; j < NF; j += 64 * W) tws[j] = tb.fft1[j];
   __syncthreads();
@@ -192,6 +199,20 @@ __global__ __launch_bounds__(64 * BR1L_WAVES, 1) void br1l_guard_kernel(
     const double2 *__restrict__ bskl, DeviceTables tb, uint32_t *__restrict__ ext_out,
     uint64_t *__restrict__ rlwe_out, int mode, unsigned long long *margin) {
   br1l_body<true>(clue_a, clue_b, lwe_a, lwe_b, bskl, tb, ext_out, rlwe_out, mode, margin);
+}
+__global__ __launch_bounds__(64 * BR1L_WAVES, 1) void br1l_from_kernel(
+    const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
+    const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
+    const double2 *__restrict__ bskl, DeviceTables tb, uint32_t *__restrict__ ext_out,
+    uint64_t *__restrict__ rlwe_out, int mode, const uint64_t *__restrict__ acc0) {
+  br1l_body<false, true>(clue_a, clue_b, lwe_a, lwe_b, bskl, tb, ext_out, rlwe_out, mode, nullptr, acc0);
+}
+__global__ __launch_bounds__(64 * BR1L_WAVES, 1) void br1l_guard_from_kernel(
+    const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
+    const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
+    const double2 *__restrict__ bskl, DeviceTables tb, uint32_t *__restrict__ ext_out,
+    uint64_t *__restrict__ rlwe_out, int mode, unsigned long long *margin, const uint64_t *__restrict__ acc0) {
+  br1l_body<true, true>(clue_a, clue_b, lwe_a, lwe_b, bskl, tb, ext_out, rlwe_out, mode, margin, acc0);
 }
 
 }  // namespace omr

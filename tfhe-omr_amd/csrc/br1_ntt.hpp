@@ -28,11 +28,13 @@ static_assert(Ntt1W::N == N1 && Ntt1W::LDS_DOUBLES * sizeof(double) >= 2 * N1 * 
 
 // Rotation g: clue g % 7 of message g / 7 (lwe_a == nullptr) or LWE g; the outputs as br1f_body's
 // (mode 0: the extracted LWE, mode 1: the full RLWE).
+// acc0 (nullptr in the production kernels): the initial accumulator is acc0's rotation instead (br1f_body's
+// FROM; a pointer tested at run time for br2l_body's reason, br2_ntt.hpp).
 __device__ __forceinline__ void br1n_body(const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b,
                                           const uint16_t *__restrict__ lwe_a, const uint16_t *__restrict__ lwe_b,
                                           const double *__restrict__ bsk1n, const DeviceTables &tb,
                                           uint32_t *__restrict__ ext, uint64_t *__restrict__ rlwe_out, int mode,
-                                          size_t g) {
+                                          size_t g, const uint64_t *acc0 = nullptr) {
   using M = Mod<1>;
   __shared__ double lds[Ntt1W::LDS_DOUBLES];  // the transforms' exchanges; [ACC, -ACC] between them
   __shared__ uint16_t la[N0];
@@ -42,8 +44,13 @@ __device__ __forceinline__ void br1n_body(const uint16_t *__restrict__ clue_a, c
   double ac[2][16];
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    ac[0][e] = 0.0;
-    ac[1][e] = lvl1_acc_init(tb, b, lane + 64 * e);
+    if (acc0) {
+      ac[0][e] = (double)lvl1_acc_from(acc0, g, 0, lane + 64 * e);
+      ac[1][e] = (double)lvl1_acc_from(acc0, g, 1, lane + 64 * e);
+    } else {
+      ac[0][e] = 0.0;
+      ac[1][e] = lvl1_acc_init(tb, b, lane + 64 * e);
+    }
   }
   __syncthreads();
   int *st = reinterpret_cast<int *>(lds);
@@ -117,6 +124,15 @@ __global__ __launch_bounds__(64) void br1n_fallback_kernel(const uint16_t *__res
                                                            const unsigned long long *lmargin, double thr) {
   if (blockIdx.x >= nrot || !margin_breached(lmargin, thr)) return;
   br1n_body(clue_a, clue_b, lwe_a, lwe_b, bsk1n, tb, ext, rlwe_out, mode, blockIdx.x);
+}
+// Both of the above from acc0, as one kernel (lmargin == nullptr: unconditional).
+__global__ __launch_bounds__(64) void br1n_from_kernel(
+    const uint16_t *__restrict__ clue_a, const uint16_t *__restrict__ clue_b, const uint16_t *__restrict__ lwe_a,
+    const uint16_t *__restrict__ lwe_b, const double *__restrict__ bsk1n, DeviceTables tb,
+    uint32_t *__restrict__ ext, uint64_t *__restrict__ rlwe_out, int mode, size_t nrot,
+    const unsigned long long *lmargin, double thr, const uint64_t *__restrict__ acc0) {
+  if (blockIdx.x >= nrot || (lmargin && !margin_breached(lmargin, thr))) return;
+  br1n_body(clue_a, clue_b, lwe_a, lwe_b, bsk1n, tb, ext, rlwe_out, mode, blockIdx.x, acc0);
 }
 
 }  // namespace omr

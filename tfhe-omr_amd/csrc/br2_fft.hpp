@@ -355,10 +355,14 @@ __device__ __forceinline__ void br2f_trace(const Br2Lds &lds, const double2 *__r
 // use rewrites a buffer whose readers have passed a later barrier: 17 workgroup barriers per step
 // (one at the step start: the previous update visible to the rotated reads).
 // LDS: twiddles 16 KB, X0 / X1 32 KB, ACC 32 KB (80 KB: two workgroups per CU).
-template <bool G>
+// FROM (the test entries omr_blind_rotate_level2_from): the initial accumulator is acc0's message
+// (canonical u64 [2][N2], the output's layout) instead; separate kernels, so that the production
+// kernels' code does not move.
+template <bool G, bool FROM = false>
 __device__ __forceinline__ void br2f_body(const uint32_t *__restrict__ lwe_int, const double2 *__restrict__ bskf,
                                           const double2 *__restrict__ twg, DeviceTables tb, uint64_t *__restrict__ out,
-                                          unsigned long long *margin, double2 *pool, size_t item) {
+                                          unsigned long long *margin, double2 *pool, size_t item,
+                                          const uint64_t *__restrict__ acc0 = nullptr) {
   using F = Fft1024;
   using M = Mod<2>;
   constexpr int E = F::E, NN = N2;
@@ -370,7 +374,17 @@ __device__ __forceinline__ void br2f_body(const uint32_t *__restrict__ lwe_int, 
   const int t = threadIdx.x;
   const uint32_t *lwe = lwe_int + item * (NI + 1);
   F::load_twiddles(tws, twg, t);
-  {  // ACC = (0, X^{-b} * LUT2)
+  if constexpr (FROM) {  // ACC = the caller's
+    const uint64_t *a0 = acc0 + item * 2 * NN;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int c = F::idx(0, t, e) + F::n * h;
+        acs[F::slot_stage(c)] = from_u64<M>(a0[c]);
+        acs[NN + F::slot_stage(c)] = from_u64<M>(a0[NN + c]);
+      }
+  } else {  // ACC = (0, X^{-b} * LUT2)
     const int b = (int)lwe[NI];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -522,6 +536,23 @@ __global__ __launch_bounds__(256, 2) void br2f_guard_kernel(const uint32_t *__re
                                                             uint64_t *__restrict__ out, unsigned long long *margin) {
   __shared__ double2 pool[BR2_LDS_BYTES / sizeof(double2)];
   br2f_body<true>(lwe_int, bskf, twg, tb, out, margin, pool, blockIdx.x);
+}
+__global__ __launch_bounds__(256, 2) void br2f_from_kernel(const uint32_t *__restrict__ lwe_int,
+                                                           const double2 *__restrict__ bskf,
+                                                           const double2 *__restrict__ twg, DeviceTables tb,
+                                                           uint64_t *__restrict__ out,
+                                                           const uint64_t *__restrict__ acc0) {
+  __shared__ double2 pool[BR2_LDS_BYTES / sizeof(double2)];
+  br2f_body<false, true>(lwe_int, bskf, twg, tb, out, nullptr, pool, blockIdx.x, acc0);
+}
+__global__ __launch_bounds__(256, 2) void br2f_guard_from_kernel(const uint32_t *__restrict__ lwe_int,
+                                                                 const double2 *__restrict__ bskf,
+                                                                 const double2 *__restrict__ twg, DeviceTables tb,
+                                                                 uint64_t *__restrict__ out,
+                                                                 unsigned long long *margin,
+                                                                 const uint64_t *__restrict__ acc0) {
+  __shared__ double2 pool[BR2_LDS_BYTES / sizeof(double2)];
+  br2f_body<true, true>(lwe_int, bskf, twg, tb, out, margin, pool, blockIdx.x, acc0);
 }
 
 

@@ -111,8 +111,13 @@ __device__ __forceinline__ void cmux_mac(const uint32_t (&pk)[BR2_E][Digits2::DW
 // output-A partial to group 0 through `part`; each group then runs one inverse transform. Output:
 // the blind rotation in the coefficient domain, u64 [2][N2] (mode 1 of br2f_kernel); trace_kernel
 // finishes mode 0.
+// acc0 (the test entries omr_blind_rotate_level2_from; nullptr in the production kernels, where the
+// branch folds away): the initial accumulator is acc0's message (canonical u64 [2][N2], the output's
+// layout) instead. A pointer tested at run time, not a template flag: as a template instantiation
+// this body compiled to different code in br2l_kernel (192 instead of 194 VGPRs, another schedule).
 __device__ __forceinline__ void br2l_body(const uint32_t *__restrict__ lwe_int, const double *__restrict__ bsk2,
-                                          DeviceTables tb, uint64_t *__restrict__ out) {
+                                          DeviceTables tb, uint64_t *__restrict__ out,
+                                          const uint64_t *acc0 = nullptr) {
   using M = Mod<2>;
   constexpr int T = BR2_T, E = BR2_E, N = N2;
   using NTT = CmuxNtt;
@@ -125,9 +130,15 @@ __device__ __forceinline__ void br2l_body(const uint32_t *__restrict__ lwe_int, 
   const uint32_t *lwe = lwe_int + (size_t)blockIdx.x * (NI + 1);
   double acc[E];
   {
-    const int b = (int)lwe[NI];
+    if (acc0) {
+      const uint64_t *a0 = acc0 + (size_t)blockIdx.x * 2 * N + (size_t)g * N;
 #pragma unroll
-    for (int e = 0; e < E; ++e) acc[e] = g == 1 ? acc2_init(tb.lut2, b, t + e * T) : 0.0;
+      for (int e = 0; e < E; ++e) acc[e] = from_u64<M>(a0[t + e * T]);
+    } else {
+      const int b = (int)lwe[NI];
+#pragma unroll
+      for (int e = 0; e < E; ++e) acc[e] = g == 1 ? acc2_init(tb.lut2, b, t + e * T) : 0.0;
+    }
     cmux_tables(tws, tb);
     __syncthreads();
   }
@@ -169,6 +180,15 @@ __global__ __launch_bounds__(BR2L_T, 1) void br2l_fallback_kernel(const uint32_t
                                                                   const unsigned long long *lmargin, double thr) {
   if (!margin_breached(lmargin, thr)) return;
   br2l_body(lwe_int, bsk2, tb, out);
+}
+// Both of the above from acc0, as one kernel (lmargin == nullptr: unconditional).
+__global__ __launch_bounds__(BR2L_T, 1) void br2l_from_kernel(const uint32_t *__restrict__ lwe_int,
+                                                              const double *__restrict__ bsk2, DeviceTables tb,
+                                                              uint64_t *__restrict__ out,
+                                                              const unsigned long long *lmargin, double thr,
+                                                              const uint64_t *__restrict__ acc0) {
+  if (lmargin && !margin_breached(lmargin, thr)) return;
+  br2l_body(lwe_int, bsk2, tb, out, acc0);
 }
 
 // ---- level 2 over two CUs per message --------------------------------------------------------
@@ -428,6 +448,16 @@ __global__ __launch_bounds__(BR2_T, 2) void trace_fallback_kernel(uint64_t *__re
                                                                   double thr) {
   if (!margin_breached(lmargin, thr)) return;
   trace_body(io, tk, tb);
+}
+
+// omr_trace's guarded run: the saved input back in place ahead of trace_fallback_kernel (same condition;
+// within launch_br2 the fallback rotation rewrites the trace's input instead)
+__global__ __launch_bounds__(BR2_T, 2) void trace_restore_kernel(uint64_t *__restrict__ io,
+                                                                 const uint64_t *__restrict__ saved,
+                                                                 const unsigned long long *lmargin, double thr) {
+  if (!margin_breached(lmargin, thr)) return;
+  const size_t base = (size_t)blockIdx.x * 2 * N2;
+  for (int j = threadIdx.x; j < 2 * N2; j += BR2_T) io[base + j] = saved[base + j];
 }
 
 // hom_trace of the latency path over TRACE_X workgroups (CUs) per message: every workgroup keeps

@@ -88,21 +88,39 @@ omr_status launch_ks(omr_ctx *c, int B, uint32_t *out, hipStream_t st) {
 // Level-1 blind rotations of n (message, clue) pairs (mode 0: clue g % 7 of message g / 7 ->
 // extracted LWE; mode 1: explicit LWEs -> full RLWE), BR1F_WPG rotations per workgroup.
 // `msgs`: the messages of the chunk (selects the latency kernels, one workgroup per rotation).
+// acc0 (the test entry omr_blind_rotate_level1_from): the rotations' initial accumulators (device,
+// canonical u64 [n][2][N1]); the same selection, on each kernel's _from instantiation.
 omr_status launch_br1(omr_ctx *c, size_t n, const uint16_t *ca, const uint16_t *cb,
                       const uint16_t *la, const uint16_t *lb, uint32_t *ext, uint64_t *rlwe, int mode,
-                      hipStream_t st, size_t msgs) {
+                      hipStream_t st, size_t msgs, const uint64_t *acc0 = nullptr) {
   const omr_ctx::Keys &k = c->keys;
   const DeviceTables &tb = c->tab.tb;
   unsigned long long *word = c->ex.margin + 2;
   if (c->ex.exact1) {  // the reference's arithmetic for every rotation (omr_ctx_set_exact_level1)
-    br1n_kernel<<<(unsigned)n, 64, 0, st>>>(ca, cb, la, lb, k.bsk1n, tb, ext, rlwe, mode, n);
+    if (acc0)
+      br1n_from_kernel<<<(unsigned)n, 64, 0, st>>>(ca, cb, la, lb, k.bsk1n, tb, ext, rlwe, mode, n, nullptr, 0.0, acc0);
+    else
+      br1n_kernel<<<(unsigned)n, 64, 0, st>>>(ca, cb, la, lb, k.bsk1n, tb, ext, rlwe, mode, n);
     HIP_TRY(hipGetLastError());
     return OMR_OK;
   }
   const unsigned g1 = (unsigned)((n + BR1F_WPG - 1) / BR1F_WPG);
   const bool g = guarded(c, 0);
   if (g) OMR_TRY(guard_begin(c, 0, st));
-  if (latency_path(c, msgs)) {
+  if (acc0) {
+    if (latency_path(c, msgs)) {
+      if (g)
+        br1l_guard_from_kernel<<<(unsigned)n, 64 * BR1L_WAVES, 0, st>>>(ca, cb, la, lb, k.bsk1l, tb, ext, rlwe, mode,
+                                                                         word, acc0);
+      else
+        br1l_from_kernel<<<(unsigned)n, 64 * BR1L_WAVES, 0, st>>>(ca, cb, la, lb, k.bsk1l, tb, ext, rlwe, mode, acc0);
+    } else if (g) {
+      br1f_guard_from_kernel<<<g1, 64 * BR1F_WPG, 0, st>>>(ca, cb, la, lb, k.bsk1f, tb, ext, rlwe, mode, n, word,
+                                                          acc0);
+    } else {
+      br1f_from_kernel<<<g1, 64 * BR1F_WPG, 0, st>>>(ca, cb, la, lb, k.bsk1f, tb, ext, rlwe, mode, n, acc0);
+    }
+  } else if (latency_path(c, msgs)) {
     if (g)
       br1l_guard_kernel<<<(unsigned)n, 64 * BR1L_WAVES, 0, st>>>(ca, cb, la, lb, k.bsk1l, tb, ext, rlwe, mode, word);
     else
@@ -116,8 +134,12 @@ omr_status launch_br1(omr_ctx *c, size_t n, const uint16_t *ca, const uint16_t *
   if (!g) return OMR_OK;
   // the exactness contract: a guarded launch whose margin reached 1 - E1 is recomputed on the exact
   // NTT in the same stream order (every workgroup leaves at once otherwise)
-  br1n_fallback_kernel<<<(unsigned)n, 64, 0, st>>>(ca, cb, la, lb, k.bsk1n, tb, ext, rlwe, mode, n, word,
-                                                   c->ex.thr[0]);
+  if (acc0)
+    br1n_from_kernel<<<(unsigned)n, 64, 0, st>>>(ca, cb, la, lb, k.bsk1n, tb, ext, rlwe, mode, n, word, c->ex.thr[0],
+                                                 acc0);
+  else
+    br1n_fallback_kernel<<<(unsigned)n, 64, 0, st>>>(ca, cb, la, lb, k.bsk1n, tb, ext, rlwe, mode, n, word,
+                                                     c->ex.thr[0]);
   HIP_TRY(hipGetLastError());
   return guard_end(c, 0, st);
 }
@@ -203,13 +225,35 @@ omr_status launch_trace_x(omr_ctx *c, size_t n, uint64_t *io, hipStream_t st, bo
                      dim3(BR2_T), args, st, launched);
 }
 
+// The trace of n level-2 rotations in place (launch_br2's mode 0): on the FFT when its a priori bound
+// allows (throughput; g: the guarded kernel), else the NTT; over TRACE_X CUs per message on the
+// latency path when the cooperative launch fits.
+omr_status launch_trace(omr_ctx *c, size_t n, uint64_t *out, hipStream_t st, bool lat, bool g) {
+  const omr_ctx::Keys &k = c->keys;
+  const DeviceTables &tb = c->tab.tb;
+  const double2 *fft2 = c->tab.fft2;
+  bool multi = false;
+  if (lat) OMR_TRY(launch_trace_x(c, n, out, st, &multi));
+  if (lat || !c->ex.trace_fft) {
+    if (!multi) trace_kernel<<<(unsigned)n, BR2_T, 0, st>>>(out, k.tk, tb);
+  } else if (g) {
+    trace_fft_guard_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(out, k.tkf, fft2, tb, c->ex.margin + 3);
+  } else {
+    trace_fft_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(out, k.tkf, fft2, tb);
+  }
+  HIP_TRY(hipGetLastError());
+  return OMR_OK;
+}
+
 // Level-2 blind rotation of n LWE(670, 4096) ciphertexts and (mode 0) the trace, always a launch of
 // its own; `mid` (optional) is recorded between the two. The latency path gives a message two CUs
 // (or two 4-wave groups) and traces in place. The throughput path's exactness contract: a guarded
 // pair notes both kernels' rounding margins in level 2's word, and a pair whose margin reaches the
 // threshold is re-run on the exact NTT (every workgroup of the fallbacks leaves at once otherwise).
+// acc0 (the test entry omr_blind_rotate_level2_from): the initial accumulators (device, canonical
+// u64 [n][2][N2]); the same selection, on each kernel's _from instantiation.
 omr_status launch_br2(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t *out, int mode, hipStream_t st,
-                      hipEvent_t mid = nullptr) {
+                      hipEvent_t mid = nullptr, const uint64_t *acc0 = nullptr) {
   const omr_ctx::Keys &k = c->keys;
   const DeviceTables &tb = c->tab.tb;
   const double2 *fft2 = c->tab.fft2;
@@ -217,32 +261,52 @@ omr_status launch_br2(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t *o
   const bool lat = latency_path(c, n), g = !lat && guarded(c, 1);
   if (lat) {
     bool two_cu = false;
-    OMR_TRY(launch_br2xy(c, n, lwe_int, out, st, &two_cu));
-    if (!two_cu) br2l_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out);
+    // (the two-CU kernels br2x / br2y take no acc0: with the override their existing code did not
+    // compile unchanged, so an override on the latency path runs the one-workgroup kernel)
+    if (!acc0) OMR_TRY(launch_br2xy(c, n, lwe_int, out, st, &two_cu));
+    if (acc0)
+      br2l_from_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, nullptr, 0.0, acc0);
+    else if (!two_cu)
+      br2l_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out);
   } else if (g) {
     OMR_TRY(guard_begin(c, 1, st));
-    br2f_guard_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, word);
+    if (acc0)
+      br2f_guard_from_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, word, acc0);
+    else
+      br2f_guard_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, word);
+  } else if (acc0) {
+    br2f_from_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, acc0);
   } else {
     br2f_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out);
   }
   HIP_TRY(hipGetLastError());
   if (mid) HIP_TRY(hipEventRecord(mid, st));
-  if (mode == 0) {  // on the FFT when its a priori bound allows (throughput), else the NTT
-    bool multi = false;
-    if (lat) OMR_TRY(launch_trace_x(c, n, out, st, &multi));
-    if (lat || !c->ex.trace_fft) {
-      if (!multi) trace_kernel<<<(unsigned)n, BR2_T, 0, st>>>(out, k.tk, tb);
-    } else if (g) {
-      trace_fft_guard_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(out, k.tkf, fft2, tb, word);
-    } else {
-      trace_fft_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(out, k.tkf, fft2, tb);
-    }
-    HIP_TRY(hipGetLastError());
-  }
+  if (mode == 0) OMR_TRY(launch_trace(c, n, out, st, lat, g));
   if (!g) return OMR_OK;
-  br2l_fallback_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, word, c->ex.thr[1]);
+  if (acc0)
+    br2l_from_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, word, c->ex.thr[1], acc0);
+  else
+    br2l_fallback_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, word, c->ex.thr[1]);
   HIP_TRY(hipGetLastError());
   if (mode == 0) trace_fallback_kernel<<<(unsigned)n, BR2_T, 0, st>>>(out, k.tk, tb, word, c->ex.thr[1]);
+  HIP_TRY(hipGetLastError());
+  return guard_end(c, 1, st);
+}
+
+// The trace alone, in place on n coefficient-domain RLWEs (the test entry omr_trace): launch_br2's
+// mode-0 selection, guard and fallback without a rotation. A guarded run saves the input first: the
+// FFT trace works in place, and the fallback recomputes from the input.
+omr_status launch_trace_only(omr_ctx *c, size_t n, uint64_t *io, uint64_t *saved, hipStream_t st) {
+  const bool lat = latency_path(c, n), g = !lat && guarded(c, 1);
+  if (g) {
+    OMR_TRY(guard_begin(c, 1, st));
+    HIP_TRY(hipMemcpyAsync(saved, io, n * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  }
+  OMR_TRY(launch_trace(c, n, io, st, lat, g));
+  if (!g) return OMR_OK;
+  trace_restore_kernel<<<(unsigned)n, BR2_T, 0, st>>>(io, saved, c->ex.margin + 3, c->ex.thr[1]);
+  HIP_TRY(hipGetLastError());
+  trace_fallback_kernel<<<(unsigned)n, BR2_T, 0, st>>>(io, c->keys.tk, c->tab.tb, c->ex.margin + 3, c->ex.thr[1]);
   HIP_TRY(hipGetLastError());
   return guard_end(c, 1, st);
 }
@@ -447,19 +511,34 @@ extern "C" omr_status omr_fft1_mul(omr_ctx *c, const uint32_t *a, const uint32_t
   return OMR_OK;
 }
 
-extern "C" omr_status omr_blind_rotate_level1(omr_ctx *c, const uint16_t *la, const uint16_t *lb,
-                                              size_t n, uint64_t *out) {
-  if (!c || !la || !lb || !out || n == 0)
+// Every word of a caller-supplied accumulator below q (host, before anything is enqueued).
+static bool canonical_words(const uint64_t *v, size_t count, uint64_t q) {
+  for (size_t i = 0; i < count; ++i)
+    if (v[i] >= q) return false;
+  return true;
+}
+
+static omr_status blind_rotate_level1_impl(omr_ctx *c, const uint16_t *la, const uint16_t *lb, size_t n,
+                                           const uint64_t *acc0, uint64_t *out) {
+  if (!c || !la || (!lb && !acc0) || !out || n == 0)
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_blind_rotate_level1: bad argument");
+  if (acc0 && !canonical_words(acc0, n * 2 * N1, (uint64_t)Lvl1Int::Q))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_blind_rotate_level1_from: acc0 holds a word >= q1");
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
   DevBuf<uint16_t> da, db;
-  DevBuf<uint64_t> dout;
+  DevBuf<uint64_t> dout, dacc;
   HIP_TRY(da.alloc(n * N0));
   HIP_TRY(db.alloc(n));
   HIP_TRY(dout.alloc(n * 2 * N1));
   HIP_TRY(hipMemcpy(da, la, n * N0 * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(db, lb, n * sizeof(uint16_t), hipMemcpyHostToDevice));
+  if (acc0) {  // the LWE bodies are unused: zeros
+    HIP_TRY(hipMemset(db, 0, n * sizeof(uint16_t)));
+    HIP_TRY(dacc.alloc(n * 2 * N1));
+    HIP_TRY(hipMemcpy(dacc, acc0, n * 2 * N1 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(db, lb, n * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
   // a pending hand-off error belongs to an earlier detect call: report it before this launch (as
   // detect_device does) instead of discarding a valid level-1 output after it
   OMR_TRY(take_handoff_error(c));
@@ -467,28 +546,44 @@ extern "C" omr_status omr_blind_rotate_level1(omr_ctx *c, const uint16_t *la, co
   // per-launch margin word, shared with every other call: serialise it with them like any scratch
   ScratchLease lease;
   OMR_TRY(lease.acquire(c, c->stream));
-  OMR_TRY(launch_br1(c, n, nullptr, nullptr, da, db, nullptr, dout, 1, c->stream, n));
+  OMR_TRY(launch_br1(c, n, nullptr, nullptr, da, db, nullptr, dout, 1, c->stream, n, acc0 ? dacc.get() : nullptr));
   OMR_TRY(lease.release());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(out, dout, n * 2 * N1 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return OMR_OK;
 }
 
+extern "C" omr_status omr_blind_rotate_level1(omr_ctx *c, const uint16_t *la, const uint16_t *lb,
+                                              size_t n, uint64_t *out) {
+  if (!lb) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_blind_rotate_level1: bad argument");
+  return blind_rotate_level1_impl(c, la, lb, n, nullptr, out);
+}
+extern "C" omr_status omr_blind_rotate_level1_from(omr_ctx *c, const uint16_t *la, const uint16_t *lb,
+                                                   size_t n, const uint64_t *acc0, uint64_t *out) {
+  return blind_rotate_level1_impl(c, la, lb, n, acc0, out);
+}
+
 static omr_status second_level_impl(omr_ctx *c, const uint32_t *lwe, size_t n, uint64_t *out,
-                                    int mode) {
+                                    int mode, const uint64_t *acc0 = nullptr) {
   if (!c || !lwe || !out || n == 0)
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_second_level: bad argument");
+  if (acc0 && !canonical_words(acc0, n * 2 * N2, (uint64_t)Mod<2>::Q))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_blind_rotate_level2_from: acc0 holds a word >= q2");
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
   DevBuf<uint32_t> dl;
-  DevBuf<uint64_t> dout;
+  DevBuf<uint64_t> dout, dacc;
   HIP_TRY(dl.alloc(n * (NI + 1)));
   HIP_TRY(dout.alloc(n * 2 * N2));
   HIP_TRY(hipMemcpy(dl, lwe, n * (NI + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (acc0) {
+    HIP_TRY(dacc.alloc(n * 2 * N2));
+    HIP_TRY(hipMemcpy(dacc, acc0, n * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  }
   OMR_TRY(take_handoff_error(c));
   ScratchLease lease;  // the hand-off slots are scratch
   OMR_TRY(lease.acquire(c, c->stream));
-  OMR_TRY(launch_br2(c, n, dl, dout, mode, c->stream));
+  OMR_TRY(launch_br2(c, n, dl, dout, mode, c->stream, nullptr, acc0 ? dacc.get() : nullptr));
   OMR_TRY(lease.release());
   HIP_TRY(hipStreamSynchronize(c->stream));
   OMR_TRY(take_handoff_error(c));
@@ -502,6 +597,31 @@ extern "C" omr_status omr_second_level(omr_ctx *c, const uint32_t *lwe, size_t n
 extern "C" omr_status omr_blind_rotate_level2(omr_ctx *c, const uint32_t *lwe, size_t n,
                                               uint64_t *out) {
   return second_level_impl(c, lwe, n, out, 1);
+}
+extern "C" omr_status omr_blind_rotate_level2_from(omr_ctx *c, const uint32_t *lwe, size_t n,
+                                                   const uint64_t *acc0, uint64_t *out) {
+  return second_level_impl(c, lwe, n, out, 1, acc0);
+}
+
+extern "C" omr_status omr_trace(omr_ctx *c, const uint64_t *rlwe, size_t n, uint64_t *out) {
+  if (!c || !rlwe || !out || n == 0) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_trace: bad argument");
+  if (!canonical_words(rlwe, n * 2 * N2, (uint64_t)Mod<2>::Q))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_trace: rlwe holds a word >= q2");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<uint64_t> dio, dsaved;
+  HIP_TRY(dio.alloc(n * 2 * N2));
+  HIP_TRY(dsaved.alloc(n * 2 * N2));
+  HIP_TRY(hipMemcpy(dio, rlwe, n * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  OMR_TRY(take_handoff_error(c));
+  ScratchLease lease;  // the hand-off slots are scratch
+  OMR_TRY(lease.acquire(c, c->stream));
+  OMR_TRY(launch_trace_only(c, n, dio, dsaved, c->stream));
+  OMR_TRY(lease.release());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  OMR_TRY(take_handoff_error(c));
+  HIP_TRY(hipMemcpy(out, dio, n * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
 }
 
 #ifdef OMR_PHASE_TRACE

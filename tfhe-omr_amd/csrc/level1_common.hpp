@@ -140,6 +140,13 @@ __device__ __forceinline__ double lvl1_acc_init(const DeviceTables &tb, int b, i
   return canon_small<Mod<1>>(rot_read<N1>(tb.lut1, j, r0));
 }
 
+// Centred coefficient j of polynomial p of rotation g's caller-supplied initial accumulator (the
+// test entry omr_blind_rotate_level1_from: acc0 canonical u64 [2][N1] per rotation, the output's layout).
+__device__ __forceinline__ int lvl1_acc_from(const uint64_t *__restrict__ acc0, size_t g, int p, int j) {
+  const int v = (int)acc0[(g * 2 + p) * N1 + j];
+  return v > Lvl1Int::H ? v - Lvl1Int::Q : v;
+}
+
 // One polynomial staged with its negacyclic extension ext = [ACC, -ACC] (2N u32 = 8 KB at st), so
 // (X^a * ACC)[j] = ext[(j - a) mod 2N]: no sign fix-up per coefficient. ACC in the Lvl1Off
 // representation: ext = [ac'', H - ac''], every entry "value + H/2". n: the stored negacyclic half,

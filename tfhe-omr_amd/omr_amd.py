@@ -190,6 +190,9 @@ EXPORTS = {
     "omr_digest_read_compact": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "omr_second_level": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_blind_rotate_level2": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
+    "omr_blind_rotate_level1_from": (C.c_int, [C.c_void_p, _u16p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "omr_blind_rotate_level2_from": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "omr_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "omr_ntt": (C.c_int, [C.c_int, C.c_int, _u64p, C.c_size_t, C.c_int]),
 }
 
@@ -987,10 +990,18 @@ class Detector:
                                      out.reshape(-1)), "omr_first_level")
         return out
 
-    def blind_rotate_level1(self, lwe_a, lwe_b) -> np.ndarray:
+    def blind_rotate_level1(self, lwe_a, lwe_b=None, acc0=None) -> np.ndarray:
+        """acc0 (u64 [n][2][1024], canonical): the initial accumulators instead of (0, X^-b LUT1); lwe_b is
+        then ignored (omr_blind_rotate_level1_from)."""
         lwe_a = np.ascontiguousarray(lwe_a, dtype=np.uint16).reshape(-1, N0)
-        lwe_b = np.ascontiguousarray(lwe_b, dtype=np.uint16).reshape(-1)
         out = np.empty((lwe_a.shape[0], 2, N1), np.uint64)
+        if acc0 is not None:
+            acc0 = np.ascontiguousarray(acc0, dtype=np.uint64).reshape(lwe_a.shape[0], 2, N1)
+            _check(lib().omr_blind_rotate_level1_from(self._h, lwe_a.reshape(-1), None, lwe_a.shape[0],
+                                                      acc0.ctypes.data, out.ctypes.data),
+                   "omr_blind_rotate_level1_from")
+            return out
+        lwe_b = np.ascontiguousarray(lwe_b, dtype=np.uint16).reshape(-1)
         _check(lib().omr_blind_rotate_level1(self._h, lwe_a.reshape(-1), lwe_b, lwe_a.shape[0], out.reshape(-1)),
                "omr_blind_rotate_level1")
         return out
@@ -1010,11 +1021,26 @@ class Detector:
         _check(lib().omr_second_level(self._h, lwe.reshape(-1), lwe.shape[0], out.reshape(-1)), "omr_second_level")
         return out
 
-    def blind_rotate_level2(self, lwe_int) -> np.ndarray:
+    def blind_rotate_level2(self, lwe_int, acc0=None) -> np.ndarray:
+        """acc0 (u64 [n][2][2048], canonical): the initial accumulators instead of (0, X^-b LUT2); the LWE
+        bodies are then ignored (omr_blind_rotate_level2_from)."""
         lwe = np.ascontiguousarray(lwe_int, dtype=np.uint32).reshape(-1, NI + 1)
         out = np.empty((lwe.shape[0], 2, N2), np.uint64)
+        if acc0 is not None:
+            acc0 = np.ascontiguousarray(acc0, dtype=np.uint64).reshape(lwe.shape[0], 2, N2)
+            _check(lib().omr_blind_rotate_level2_from(self._h, lwe.reshape(-1), lwe.shape[0], acc0.ctypes.data,
+                                                      out.ctypes.data), "omr_blind_rotate_level2_from")
+            return out
         _check(lib().omr_blind_rotate_level2(self._h, lwe.reshape(-1), lwe.shape[0], out.reshape(-1)),
                "omr_blind_rotate_level2")
+        return out
+
+    def trace(self, rlwe) -> np.ndarray:
+        """The homomorphic trace alone on coefficient-domain RLWEs (u64 [n][2][2048], canonical): what
+        second_level runs after its rotation; NTT-domain output (omr_trace)."""
+        rlwe = np.ascontiguousarray(rlwe, dtype=np.uint64).reshape(-1, 2, N2)
+        out = np.empty(rlwe.shape, np.uint64)
+        _check(lib().omr_trace(self._h, rlwe.ctypes.data, rlwe.shape[0], out.ctypes.data), "omr_trace")
         return out
 
 
