@@ -656,6 +656,79 @@ omr_status omr_digest_read_compact(omr_digest *dg, int bits, void *idx_packed, v
                                    void *bitmap_packed);
 
 /* ---------------------------------------------------------------------------------------
+ * Key audit (none in the reference): check a detection key against its secret before it is uploaded and
+ * after any reload, and count non-canonical words at intake without a secret. A detector runs to
+ * completion on a damaged key and returns well-formed ciphertexts that decrypt to "not pertinent"; this
+ * is the check that finds the damage first.
+ *
+ * Arithmetic, exact integers throughout. A component c is an omr_key_component; its modulus q is q1 for
+ * BSK1 and KSK and q2 for BSK2 and TRACE; rows and row layout are those of the key layout above (4096 /
+ * 27648 / 8040 / 275 rows; an RLWE row is a[N] then b[N], a key-switching row a[670] then b). Every word
+ * is reduced mod q first; a word >= q counts as non-canonical and is still used reduced. The noise of a row
+ * is its phase minus the message the generators put there, centred into (-q/2, q/2):
+ *   BSK row (i, r), k = r mod d, mg = bit_i 2^(drop + k logB) (bit = s0 for BSK1, s_int for BSK2; s = s1, s2):
+ *     a-gadget (r < d):   e = (b - a s) + mg s     coefficient-wise; this holds for the plain row
+ *                                                  (a = alpha + mg) and for the seeded row (b carries -mg s)
+ *     b-gadget (r >= d):  e = (b - a s) - mg at coefficient 0
+ *   TRACE row (k, j), g = 2048 / 2^k + 1:  e = (b - a s2) + sigma_g(s2) 4^j
+ *   KSK row (i, j):                        e = b - <a, s_int> - s1_i 2^j mod q1   (one value per row)
+ * Per row the audit yields row_max = max |e|; per call a summary.
+ * ------------------------------------------------------------------------------------- */
+/* Added into by every key-audit call that is given one and never reset by the library: counts, a maximum
+ * and a minimum, so it does not depend on grid, staging or call order. The caller initialises it to zeros
+ * with first_row_over = UINT64_MAX (merging is by minimum). noise_bits[k] counts the noise values whose
+ * |e| has bit length k (k = 0 for e = 0); their sum is N * rows (rows for KSK: one value per row). */
+typedef struct {
+  uint64_t rows, noncanonical, max_abs_noise;
+  uint64_t rows_over;       /* rows with row_max > limit */
+  uint64_t first_row_over;  /* smallest such component row index; UINT64_MAX if none */
+  uint64_t noise_bits[OMR_AUDIT_RESIDUAL_BINS];
+} omr_key_audit_summary;
+
+/* K: the largest |e| this library's generators can draw for the component (the last index of their
+ * cumulative table, csrc/rng.hpp: 44 / 27,064 / 16 / 16). A `limit` of UINT64_MAX below means K. */
+omr_status omr_key_noise_support(int component, uint64_t *K);
+
+/* Row ranges (the kernels' entry, and the stage entry points of the tests). d_rows points at row
+ * first_row of the component in device memory of the auditor's device (16-byte aligned; 4-byte for KSK,
+ * whose rows are 2,684 bytes); d_row_max is u64 [rows]; it or d_summary may be NULL, not both. rows = 0
+ * does nothing; a component that does not exist or a range beyond it is OMR_ERR_INVALID_ARGUMENT.
+ * Enqueued on hip_stream (NULL = null stream), returns once enqueued. The first key-audit call on an
+ * auditor uploads its level-1 tables and the secrets' coefficient forms (blocking). */
+omr_status omr_audit_key_rows_device(omr_auditor *aud, int component, const void *d_rows, size_t first_row,
+                                     size_t rows, uint64_t limit, uint64_t *d_row_max,
+                                     omr_key_audit_summary *d_summary, void *hip_stream);
+/* the same results on the CPU (host memory, no GPU): the statement the kernels are checked against.
+ * nthreads <= 0: the host's cores, at most 16. */
+omr_status omr_audit_key_rows_cpu(const omr_secret_key_pack *sk, int component, const void *rows_ptr,
+                                  size_t first_row, size_t rows, uint64_t limit, uint64_t *row_max,
+                                  omr_key_audit_summary *summary, int nthreads);
+/* Whole keys: out[c] is added into for every component whose pointer is not NULL (a NULL component is
+ * skipped and its entry left untouched); limit NULL = K for every component. The view's pointers may be
+ * host memory or device memory of the auditor's device, as for omr_ctx_create; a host component is staged
+ * in pieces of omr_auditor_set_staging x 32 KiB. Returns when done. */
+omr_status omr_audit_key(omr_auditor *aud, const omr_detection_key_view *key, const uint64_t limit[4],
+                         omr_key_audit_summary out[4]);
+/* The same for a seeded key (all four bodies required, as for omr_expand_detection_key_device): expands it
+ * on the auditor's device into temporaries (380,227,584 B), audits them and frees them. */
+omr_status omr_audit_key_seeded(omr_auditor *aud, const omr_seeded_key_view *key, const uint64_t limit[4],
+                                omr_key_audit_summary out[4]);
+omr_status omr_audit_key_cpu(const omr_secret_key_pack *sk, const omr_detection_key_view *key,
+                             const uint64_t limit[4], omr_key_audit_summary out[4], int nthreads);
+/* Server side, no secret: the words >= q of its level (1: u32 against q1, 2: u64 against q2). These calls
+ * report and do not reject; omr_ctx_create* take keys exactly as before. The device count is added into
+ * *d_count on hip_stream of the current device and the call returns once enqueued; n = 0 does nothing. */
+omr_status omr_key_count_noncanonical_device(int level, const void *d_words, size_t n, uint64_t *d_count,
+                                             void *hip_stream);
+/* noncanonical[c] is written for every component whose pointer is not NULL. Host memory, or device memory
+ * of `device` (returns when done). The _seeded twins look at the bodies only: the masks come from the seed
+ * by rejection sampling and are canonical by construction. */
+omr_status omr_key_validate(const omr_detection_key_view *key, uint64_t noncanonical[4], int nthreads);
+omr_status omr_key_validate_device(const omr_detection_key_view *key, int device, uint64_t noncanonical[4]);
+omr_status omr_key_validate_seeded(const omr_seeded_key_view *key, uint64_t noncanonical[4], int nthreads);
+omr_status omr_key_validate_seeded_device(const omr_seeded_key_view *key, int device, uint64_t noncanonical[4]);
+
+/* ---------------------------------------------------------------------------------------
  * Stage entry points (for parity tests and per-stage benchmarks, benches/two_level_bs.rs).
  * Host buffers.
  * ------------------------------------------------------------------------------------- */

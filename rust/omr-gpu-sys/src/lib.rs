@@ -94,6 +94,24 @@ pub mod ffi {
                    residual_bits: [0; OMR_AUDIT_RESIDUAL_BINS] }
         }
     }
+    /// `omr_key_audit_summary`: integer tallies that every key-audit call adds into. `Default` is the
+    /// value to start from: zeros and `first_row_over = u64::MAX` (no row over the limit yet).
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub struct OmrKeyAuditSummary {
+        pub rows: u64,
+        pub noncanonical: u64,
+        pub max_abs_noise: u64,
+        pub rows_over: u64,
+        pub first_row_over: u64,
+        pub noise_bits: [u64; OMR_AUDIT_RESIDUAL_BINS],
+    }
+    impl Default for OmrKeyAuditSummary {
+        fn default() -> Self {
+            Self { rows: 0, noncanonical: 0, max_abs_noise: 0, rows_over: 0, first_row_over: u64::MAX,
+                   noise_bits: [0; OMR_AUDIT_RESIDUAL_BINS] }
+        }
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
     pub struct OmrDigestInfo {
@@ -304,6 +322,28 @@ pub mod ffi {
                                  summary: *mut OmrAuditSummary) -> OmrStatus;
         pub fn omr_digest_read_compact(dg: *mut OmrDigest, bits: c_int, idx_packed: *mut c_void,
                                        pay_packed: *mut c_void, bitmap_packed: *mut c_void) -> OmrStatus;
+
+        // key audit
+        pub fn omr_key_noise_support(component: c_int, k: *mut u64) -> OmrStatus;
+        pub fn omr_audit_key_rows_device(aud: *mut OmrAuditor, component: c_int, d_rows: *const c_void, first_row: usize,
+                                         rows: usize, limit: u64, d_row_max: *mut u64,
+                                         d_summary: *mut OmrKeyAuditSummary, hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_audit_key_rows_cpu(sk: *const OmrSecretKeyPack, component: c_int, rows_ptr: *const c_void,
+                                      first_row: usize, rows: usize, limit: u64, row_max: *mut u64,
+                                      summary: *mut OmrKeyAuditSummary, nthreads: c_int) -> OmrStatus;
+        pub fn omr_audit_key(aud: *mut OmrAuditor, key: *const OmrDetectionKeyView, limit: *const u64,
+                             out: *mut OmrKeyAuditSummary) -> OmrStatus;
+        pub fn omr_audit_key_seeded(aud: *mut OmrAuditor, key: *const OmrSeededKeyView, limit: *const u64,
+                                    out: *mut OmrKeyAuditSummary) -> OmrStatus;
+        pub fn omr_audit_key_cpu(sk: *const OmrSecretKeyPack, key: *const OmrDetectionKeyView, limit: *const u64,
+                                 out: *mut OmrKeyAuditSummary, nthreads: c_int) -> OmrStatus;
+        pub fn omr_key_count_noncanonical_device(level: c_int, d_words: *const c_void, n: usize, d_count: *mut u64,
+                                                 hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_key_validate(key: *const OmrDetectionKeyView, noncanonical: *mut u64, nthreads: c_int) -> OmrStatus;
+        pub fn omr_key_validate_device(key: *const OmrDetectionKeyView, device: c_int, noncanonical: *mut u64) -> OmrStatus;
+        pub fn omr_key_validate_seeded(key: *const OmrSeededKeyView, noncanonical: *mut u64, nthreads: c_int) -> OmrStatus;
+        pub fn omr_key_validate_seeded_device(key: *const OmrSeededKeyView, device: c_int,
+                                              noncanonical: *mut u64) -> OmrStatus;
 
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
@@ -1135,6 +1175,33 @@ impl<'a> Auditor<'a> {
                               decoded.as_mut_ptr(), summary)
         })?;
         Ok(Audit { records, decoded, summary: *summary })
+    }
+
+    /// `omr_audit_key`: a detection key in host memory against the auditor's secret, staged through the
+    /// device in pieces. One summary per component (`omr_key_component` order), started from
+    /// `Default`; `limit` `None` is the generators' noise support. A key that passes has
+    /// `rows_over == 0` in all four.
+    pub fn audit_key(&self, key: &DetectionKey, limit: Option<[u64; 4]>) -> Result<[OmrKeyAuditSummary; 4], OmrError> {
+        if key.bsk1.len() != BSK1_LEN || key.ksk.len() != KSK_LEN || key.bsk2.len() != BSK2_LEN
+            || key.trace_key.len() != TRACE_KEY_LEN
+        {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "detection key sizes".into() });
+        }
+        let view = OmrDetectionKeyView { bsk1: key.bsk1.as_ptr(), ksk: key.ksk.as_ptr(), bsk2: key.bsk2.as_ptr(),
+                                         trace_key: key.trace_key.as_ptr() };
+        let mut out = [OmrKeyAuditSummary::default(); 4];
+        let lim = limit.as_ref().map_or(std::ptr::null(), |l| l.as_ptr());
+        check(unsafe { omr_audit_key(self.raw, &view, lim, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// `omr_audit_key_seeded`: the same for a seeded key, expanded on the device into temporaries.
+    pub fn audit_seeded_key(&self, key: &SeededKey, limit: Option<[u64; 4]>) -> Result<[OmrKeyAuditSummary; 4], OmrError> {
+        let view = key.view()?;
+        let mut out = [OmrKeyAuditSummary::default(); 4];
+        let lim = limit.as_ref().map_or(std::ptr::null(), |l| l.as_ptr());
+        check(unsafe { omr_audit_key_seeded(self.raw, &view, lim, out.as_mut_ptr()) })?;
+        Ok(out)
     }
 
     /// Device buffers of the auditor's GPU (`omr_compact_expand_device`): returns once enqueued.

@@ -5,7 +5,7 @@
 // indices and their payloads come back.
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
-//           [--compact BITS] [--host-only]
+//           [--compact BITS] [--audit-key] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -25,6 +25,9 @@
 // omr_digest_read_compact), the recipient expands it (omr_compact_expand_cpu) and retrieves from that. Both
 // sizes, R(BITS) for the recipient's key and the measured residual increase are printed; an increase above R
 // or a decoded value that changed fails the run.
+// --audit-key audits the detection key it generated against the recipient's secret on the GPU before the
+// detector is created (omr_audit_key, or omr_audit_key_seeded with --seeded; include/omr_gpu.h, "Key audit"):
+// a row whose noise lies outside the generators' support, in any component, fails the run.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -66,7 +69,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false, bitmap = false, seeded = false;
+  bool audit = false, bitmap = false, seeded = false, audit_key = false;
   int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -78,10 +81,11 @@ int main(int argc, char **argv) {
     else if (a == "--bitmap") bitmap = true;
     else if (a == "--seeded") seeded = true;
     else if (a == "--compact" && i + 1 < argc) compact_bits = std::atoi(argv[++i]);
+    else if (a == "--audit-key") audit_key = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--seeded] [--compact BITS] [--host-only]\n",
+                   "[--seeded] [--compact BITS] [--audit-key] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -193,6 +197,40 @@ int main(int argc, char **argv) {
   // Detector::new + detect over the board (omr.rs:160-164)
   omr_ctx *ctx = nullptr;
   omr_detection_key_view view{bsk1.data(), ksk.data(), bsk2.data(), tk.data()};
+  if (audit_key) {
+    // the recipient's check before the key leaves: every row's noise inside the generators' support
+    static const char *const comp_name[4] = {"bsk1", "ksk", "bsk2", "trace_key"};
+    omr_auditor *ka = nullptr;
+    CHECK(omr_auditor_create(pa, device, &ka));
+    omr_key_audit_summary ks[4];
+    for (auto &k : ks) {
+      std::memset(&k, 0, sizeof k);
+      k.first_row_over = UINT64_MAX;
+    }
+    t = clk::now();
+    if (seeded) CHECK(omr_audit_key_seeded(ka, &sview, nullptr, ks));
+    else CHECK(omr_audit_key(ka, &view, nullptr, ks));
+    std::printf("key audit time: %.3f s (%s)\n", secs(t), seeded ? "seeded key, expanded on the device" : "full key, staged");
+    omr_auditor_destroy(ka);
+    bool bad = false;
+    for (int c = 0; c < 4; ++c) {
+      uint64_t K = 0;
+      CHECK(omr_key_noise_support(c, &K));
+      std::printf("key audit %-9s: %llu rows, max |e| %llu (support %llu), %llu over, %llu non-canonical words\n", comp_name[c],
+                  (unsigned long long)ks[c].rows, (unsigned long long)ks[c].max_abs_noise, (unsigned long long)K,
+                  (unsigned long long)ks[c].rows_over, (unsigned long long)ks[c].noncanonical);
+      if (ks[c].rows_over) {
+        std::printf("Fail: %s row %llu has noise outside the generators' support\n", comp_name[c],
+                    (unsigned long long)ks[c].first_row_over);
+        bad = true;
+      }
+    }
+    if (bad) {
+      std::printf("FAILED\n");
+      return 1;
+    }
+    std::printf("key audit OK\n");
+  }
   t = clk::now();
   if (seeded) CHECK(omr_ctx_create_seeded(&sview, device, &ctx));
   else CHECK(omr_ctx_create(&view, device, &ctx));

@@ -81,6 +81,12 @@ class _AuditSummary(C.Structure):
                [("residual_bits", C.c_uint64 * 50)]
 
 
+class _KeyAuditSummary(C.Structure):
+    """omr_key_audit_summary."""
+    _fields_ = [(n, C.c_uint64) for n in ("rows", "noncanonical", "max_abs_noise", "rows_over", "first_row_over")] + \
+               [("noise_bits", C.c_uint64 * 50)]
+
+
 # omr_ct_audit as a structured dtype (16 bytes)
 AUDIT_RECORD = np.dtype([("max_abs_residual", np.uint64), ("nonzero", np.uint32), ("first", np.uint32)])
 AUDIT_RESIDUAL_BINS = 50
@@ -188,6 +194,19 @@ EXPORTS = {
     "omr_audit_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "omr_digest_read_compact": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_key_noise_support": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "omr_audit_key_rows_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_audit_key_rows_cpu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_int]),
+    "omr_audit_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_audit_key_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_audit_key_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "omr_key_count_noncanonical_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "omr_key_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "omr_key_validate_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "omr_key_validate_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "omr_key_validate_seeded_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "omr_second_level": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_blind_rotate_level2": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, _u64p]),
     "omr_blind_rotate_level1_from": (C.c_int, [C.c_void_p, _u16p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -650,6 +669,112 @@ def audit_cpu(secret: "SecretKeyPack", cts, nthreads: int = 0):
                        "omr_audit_cpu", cts)
 
 
+# ---- key audit (include/omr_gpu.h, "Key audit") ----
+KEY_LIMIT_K = 2**64 - 1  # a limit that stands for the generators' noise support K
+# words per row of each component in the key layout (an RLWE row is a then b; a KSK row a[670] then b)
+KEY_ROW_ELEMS = (2 * N1, NI + 1, 2 * N2, 2 * N2)
+
+
+def key_noise_support(component: int) -> int:
+    """omr_key_noise_support: the largest |e| the generators can draw for the component."""
+    k = C.c_uint64()
+    _check(lib().omr_key_noise_support(component, C.byref(k)), "omr_key_noise_support")
+    return k.value
+
+
+def _key_summary_new() -> "_KeyAuditSummary":
+    t = _KeyAuditSummary()
+    t.first_row_over = 2**64 - 1
+    return t
+
+
+def _key_summary_dict(t: "_KeyAuditSummary") -> dict:
+    d = {n: int(getattr(t, n)) for n in ("rows", "noncanonical", "max_abs_noise", "rows_over", "first_row_over")}
+    d["noise_bits"] = np.array(t.noise_bits[:], dtype=np.uint64)
+    return d
+
+
+def key_summary_init_bytes() -> bytes:
+    """An omr_key_audit_summary to add into (440 bytes): zeros with first_row_over = UINT64_MAX."""
+    return bytes(_key_summary_new())
+
+
+def key_summary_from_bytes(buf) -> dict:
+    """The dict form of an omr_key_audit_summary copied back from the device (440 bytes)."""
+    return _key_summary_dict(_KeyAuditSummary.from_buffer_copy(bytes(buf)))
+
+
+def _key_rows(component: int, rows) -> np.ndarray:
+    if not 0 <= component < 4:
+        return np.ascontiguousarray(rows).reshape(1, -1)  # the library reports the component
+    return np.ascontiguousarray(rows, dtype=KEY_COMPONENTS[component][2]).reshape(-1, KEY_ROW_ELEMS[component])
+
+
+def audit_key_rows_cpu(secret: "SecretKeyPack", component: int, rows, first_row: int = 0, limit: int = KEY_LIMIT_K,
+                       nthreads: int = 0, n_rows: int = None):
+    """omr_audit_key_rows_cpu over host rows [n][row words] that start at component row first_row:
+    (row_max u64 [n], summary dict)."""
+    r = _key_rows(component, rows)
+    n = r.shape[0] if n_rows is None else n_rows
+    row_max = np.zeros(max(n, 0), np.uint64)
+    t = _key_summary_new()
+    _check(lib().omr_audit_key_rows_cpu(secret._h, component, r.ctypes.data, first_row, n, limit, row_max.ctypes.data,
+                                        C.addressof(t), nthreads), "omr_audit_key_rows_cpu")
+    return row_max, _key_summary_dict(t)
+
+
+def _limits(limit):
+    return None if limit is None else (C.c_uint64 * 4)(*limit)
+
+
+def _key_view(key) -> "_KeyView":
+    """A DetectionKey (host arrays) or four raw pointers (host or device memory; 0 skips a component)."""
+    if isinstance(key, DetectionKey):
+        arrs = [np.ascontiguousarray(a) for a in (key.bsk1, key.ksk, key.bsk2, key.trace_key)]
+        v = _KeyView(*[a.ctypes.data for a in arrs])
+        v._keep = arrs
+        return v
+    return _KeyView(*[p or None for p in key])
+
+
+def _key_audit_whole(call, what, view, limit):
+    out = (_KeyAuditSummary * 4)(*[_key_summary_new() for _ in range(4)])
+    _check(call(C.byref(view), _limits(limit), out), what)
+    return [_key_summary_dict(t) for t in out]
+
+
+def audit_key_cpu(secret: "SecretKeyPack", key, limit=None, nthreads: int = 0):
+    """omr_audit_key_cpu: the four summaries (omr_key_component order) of a key in host memory."""
+    return _key_audit_whole(lambda v, l, o: lib().omr_audit_key_cpu(secret._h, v, l, o, nthreads), "omr_audit_key_cpu",
+                            _key_view(key), limit)
+
+
+def validate_key(key, device: int = None, nthreads: int = 0) -> list:
+    """Words >= q per component, without a secret: omr_key_validate* of a DetectionKey / SeededKey in host
+    memory, or with `device` of four raw device pointers (a fifth entry, the mask seed, marks a seeded key's
+    bodies)."""
+    out = (C.c_uint64 * 4)()
+    seeded = isinstance(key, SeededKey) or (not isinstance(key, DetectionKey) and len(key) == 5)
+    if isinstance(key, SeededKey):
+        view = key._view()
+    elif seeded:
+        view = _SeededKeyView(*[p or None for p in key[:4]], key[4])
+    else:
+        view = _key_view(key)
+    name = "omr_key_validate" + ("_seeded" if seeded else "") + ("" if device is None else "_device")
+    if device is None:
+        _check(getattr(lib(), name)(C.byref(view), out, nthreads), name)
+    else:
+        _check(getattr(lib(), name)(C.byref(view), device, out), name)
+    return [int(v) for v in out]
+
+
+def key_count_noncanonical_device(level: int, d_words: int, n: int, d_count: int, stream: int = 0) -> None:
+    """omr_key_count_noncanonical_device: adds the words >= q of the level into the u64 at d_count."""
+    _check(lib().omr_key_count_noncanonical_device(level, d_words or None, n, d_count or None, stream or None),
+           "omr_key_count_noncanonical_device")
+
+
 class Auditor:
     """omr_auditor: the level-2 secret on one device; decrypts, classifies and noise-audits
     NttRlweCiphertexts (pertinency vectors, digests) on the GPU. The counterpart of the reference's
@@ -704,6 +829,33 @@ class Auditor:
         on `stream`; the caller synchronises."""
         _check(lib().omr_compact_expand_device(self._h, d_packed or None, n, bits, d_cts or None, stream or None),
                "omr_compact_expand_device")
+
+    def audit_key(self, key, limit=None) -> list:
+        """omr_audit_key: the four summaries (omr_key_component order) of a DetectionKey in host memory or of
+        four raw pointers (host or device memory of the auditor's device; 0 skips a component). limit: four
+        values, None = the generators' support K."""
+        return _key_audit_whole(lambda v, l, o: lib().omr_audit_key(self._h, v, l, o), "omr_audit_key", _key_view(key),
+                                limit)
+
+    def audit_seeded_key(self, key, limit=None) -> list:
+        """omr_audit_key_seeded: a SeededKey (host bodies) or (bsk1_b, ksk_b, bsk2_b, trace_key_b, mask_seed)
+        raw pointers, expanded on the device into temporaries and audited there."""
+        view = key._view() if isinstance(key, SeededKey) else _SeededKeyView(*[p or None for p in key[:4]], key[4])
+        return _key_audit_whole(lambda v, l, o: lib().omr_audit_key_seeded(self._h, v, l, o), "omr_audit_key_seeded",
+                                view, limit)
+
+    def audit_key_cpu(self, key, limit=None, nthreads: int = 0) -> list:
+        """The same results from omr_audit_key_cpu."""
+        return audit_key_cpu(self._sk, key, limit, nthreads)
+
+    def audit_key_rows(self, component: int, d_rows: int, first_row: int, rows: int, limit: int = KEY_LIMIT_K,
+                       d_row_max: int = 0, d_summary: int = 0, stream: int = 0) -> None:
+        """Device pointers (omr_audit_key_rows_device): d_rows at component row first_row, d_row_max u64 [rows],
+        d_summary 440 bytes that are added into (key_summary_init_bytes()); 0 skips an output. Enqueued on
+        `stream`; the caller synchronises."""
+        _check(lib().omr_audit_key_rows_device(self._h, component, d_rows or None, first_row, rows, limit,
+                                               d_row_max or None, d_summary or None, stream or None),
+               "omr_audit_key_rows_device")
 
     @staticmethod
     def summary_from_bytes(buf) -> dict:
