@@ -656,6 +656,85 @@ omr_status omr_digest_read_compact(omr_digest *dg, int bits, void *idx_packed, v
                                    void *bitmap_packed);
 
 /* ---------------------------------------------------------------------------------------
+ * Indexed payload weights (none in the reference): payload weights that are a function of (seed,
+ * combination, global message index) alone, so that no party draws or holds a board-wide table.
+ * omr_payload_weights restates the reference's one sequential StdRng stream with rejection
+ * (detector.rs:376-387): weight (j, i) is known only after j * all + i draws, and the detector, every
+ * shard and the recipient each build the whole [combinations][all] table. Here, with key[0..7] the
+ * little-endian words of the 32-byte weight seed exactly as in omr_payload_weights, for combination
+ * j < 2^32 and global message index g:
+ *   B      = chacha_block(12, key, counter = g >> 4, stream = (0x70617977 << 32) | j)      ("payw")
+ *   w(j,g) = (uint64_t)B[g & 15] * 257 >> 32     for j <  combination_count, in [0, 256]
+ *   w(j,g) = 0                                   for j >= combination_count (a padding combination)
+ * One block holds one combination's weights for 16 consecutive messages.
+ *
+ * Stream separation. The reference stream (omr_payload_weights) uses stream id 0 and the index buckets
+ * "bukt"; the stream id here is never 0, so the streams never share a block.
+ * No rejection step, so the index is random-access. Each residue receives 16,711,935 or 16,711,936 of
+ * the 2^32 words: a relative bias below 6.1e-8. The solve's invertibility argument (i.i.d. near-uniform
+ * entries mod 257) is untouched.
+ *
+ * Everything else of the payload digest is unchanged: the slot layout, the centred lift, the NTT, the
+ * sum mod q2, cmb_count_per_cipher and omr_get_retrieval_params. An indexed digest is an ordinary payload
+ * digest: any partition of a board, any shard and any merge give the same bits, and it is compacted,
+ * audited and merged like any other. The two conventions do not mix: a digest encoded with indexed
+ * weights is solved with omr_retrieve_payloads_indexed (or omr_retrieve_payloads given the indexed table).
+ * ------------------------------------------------------------------------------------- */
+/* Host, parallel (nthreads <= 0: the host's cores, at most 16): out u16 [n_combos][n_indices], out[r][k] =
+ * w(first_combo + r, indices[k]); rows at or beyond combination_count are zero. The recipient's matrix is
+ * (combination_count, 0, combination_count, its indices); any index of size_t is valid (no board size
+ * enters). Sorted indices reuse a block. n_combos = 0 or n_indices = 0 does nothing. */
+omr_status omr_indexed_weights_at(const uint8_t seed[32], uint32_t combination_count, uint32_t first_combo,
+                                  uint32_t n_combos, const size_t *indices, size_t n_indices, uint16_t *out,
+                                  int nthreads);
+/* The indexed weights in omr_payload_weights's layout, out u16 [cmb_cipher_count * cmb_count_per_cipher][all]
+ * (padding rows zero), for cross-checks and for callers that keep the table path: on the host, and into a
+ * device buffer of the current HIP device on hip_stream (NULL = null stream; returns once enqueued).
+ * OMR_ERR_INVALID_ARGUMENT for NULL, all = 0, or fewer rows than combinations. */
+omr_status omr_indexed_weights_table(const uint8_t seed[32], size_t all_payloads_count, uint32_t combination_count,
+                                     uint32_t cmb_cipher_count, uint32_t cmb_count_per_cipher, uint16_t *out,
+                                     int nthreads);
+omr_status omr_indexed_weights_table_device(const uint8_t seed[32], size_t all_payloads_count,
+                                            uint32_t combination_count, uint32_t cmb_cipher_count,
+                                            uint32_t cmb_count_per_cipher, uint16_t *d_out, void *hip_stream);
+/* omr_encode_payloads_device with indexed weights computed in the kernel: no table. Covers the payload
+ * ciphertexts [first_ct, first_ct + n_ct), which hold the combinations first_ct * cmb_per_ct ..; a caller
+ * can therefore encode a large digest in groups of ciphertexts. Combinations at or beyond
+ * combination_count are padding: a ciphertext that holds only padding is all zeros. d_out u64
+ * [n_ct][2][2048]; the same bits as omr_encode_payloads_device fed omr_indexed_weights_table_device's
+ * table. OMR_ERR_INVALID_ARGUMENT, before anything is enqueued, for NULL (seed included), n_ct = 0 or above
+ * 65,535, cmb_per_ct = 0 or cmb_per_ct * 612 > 2048, or global_offset + D > all_payloads_count. */
+omr_status omr_encode_payloads_indexed_device(omr_ctx *ctx, const uint64_t *d_pv, const uint16_t *d_payloads,
+                                              size_t D, size_t global_offset, size_t all_payloads_count,
+                                              const uint8_t seed[32], uint32_t combination_count,
+                                              uint32_t first_ct, uint32_t n_ct, uint32_t cmb_per_ct,
+                                              uint64_t *d_out /* [n_ct][2][2048] */, void *hip_stream);
+/* The same on host buffers; returns when done. */
+omr_status omr_encode_payloads_indexed(omr_ctx *ctx, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                       size_t global_offset, size_t all_payloads_count, const uint8_t seed[32],
+                                       uint32_t combination_count, uint32_t first_ct, uint32_t n_ct,
+                                       uint32_t cmb_per_ct, uint64_t *out);
+/* omr_digest_begin for a session whose payload digest uses indexed weights: it draws, uploads and holds no
+ * weights (the call does not block on a table) and runs the indexed kernel per piece. Device footprint: the
+ * running digest, one detect chunk of pertinency ciphertexts and the host updates' staging, none of which
+ * grows with all_payloads_count. Every other session call behaves as documented above; the index digest
+ * and the bitmap are those of an omr_digest_begin session on the same inputs. */
+omr_status omr_digest_begin_indexed(omr_ctx *ctx, size_t all_payloads_count, size_t pertinent_count,
+                                    uint64_t index_seed, const uint8_t weight_seed[32], void *hip_stream,
+                                    omr_digest **out);
+/* The bytes of device memory a session owns now (*total: weights, running digest, pertinency chunk, host
+ * staging, merge staging, bitmap, compact buffer) and the weights' share of them (*weights: 0 for an
+ * indexed session, always). Not poisoned-sensitive; touches no stream. */
+omr_status omr_digest_device_bytes(omr_digest *dg, size_t *total, size_t *weights);
+/* omr_retrieve_payloads for an indexed digest: the same decode and the same elimination, the matrix
+ * taken from omr_indexed_weights_at (combination_count x n_indices values; no table). The same status
+ * codes, OMR_ERR_NOT_INVERTIBLE included. */
+omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
+                                         size_t all_payloads_count, uint32_t combination_count,
+                                         const uint8_t weight_seed[32], const size_t *indices, size_t n_indices,
+                                         uint16_t *payloads);
+
+/* ---------------------------------------------------------------------------------------
  * Key audit (none in the reference): check a detection key against its secret before it is uploaded and
  * after any reload, and count non-canonical words at intake without a secret. A detector runs to
  * completion on a damaged key and returns well-formed ciphertexts that decrypt to "not pertinent"; this

@@ -292,6 +292,34 @@ pub mod ffi {
         pub fn omr_digest_read_bitmap(dg: *mut OmrDigest, bitmap_cts: *mut u64) -> OmrStatus;
         pub fn omr_digest_merge_bitmap(dg: *mut OmrDigest, bitmap_cts: *const u64) -> OmrStatus;
 
+        // indexed payload weights (none in the reference)
+        pub fn omr_indexed_weights_at(seed: *const u8, combination_count: u32, first_combo: u32, n_combos: u32,
+                                      indices: *const usize, n_indices: usize, out: *mut u16,
+                                      nthreads: c_int) -> OmrStatus;
+        pub fn omr_indexed_weights_table(seed: *const u8, all_payloads_count: usize, combination_count: u32,
+                                         cmb_cipher_count: u32, cmb_count_per_cipher: u32, out: *mut u16,
+                                         nthreads: c_int) -> OmrStatus;
+        pub fn omr_indexed_weights_table_device(seed: *const u8, all_payloads_count: usize, combination_count: u32,
+                                                cmb_cipher_count: u32, cmb_count_per_cipher: u32, d_out: *mut u16,
+                                                hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_encode_payloads_indexed_device(ctx: *mut OmrCtx, d_pv: *const u64, d_payloads: *const u16,
+                                                  d: usize, global_offset: usize, all_payloads_count: usize,
+                                                  seed: *const u8, combination_count: u32, first_ct: u32,
+                                                  n_ct: u32, cmb_per_ct: u32, d_out: *mut u64,
+                                                  hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_encode_payloads_indexed(ctx: *mut OmrCtx, pv: *const u64, payloads: *const u16, d: usize,
+                                           global_offset: usize, all_payloads_count: usize, seed: *const u8,
+                                           combination_count: u32, first_ct: u32, n_ct: u32, cmb_per_ct: u32,
+                                           out: *mut u64) -> OmrStatus;
+        pub fn omr_digest_begin_indexed(ctx: *mut OmrCtx, all_payloads_count: usize, pertinent_count: usize,
+                                        index_seed: u64, weight_seed: *const u8, hip_stream: *mut c_void,
+                                        out: *mut *mut OmrDigest) -> OmrStatus;
+        pub fn omr_digest_device_bytes(dg: *mut OmrDigest, total: *mut usize, weights: *mut usize) -> OmrStatus;
+        pub fn omr_retrieve_payloads_indexed(sk: *const OmrSecretKeyPack, pay_cts: *const u64, n_ct: u32,
+                                             all_payloads_count: usize, combination_count: u32,
+                                             weight_seed: *const u8, indices: *const usize, n_indices: usize,
+                                             payloads: *mut u16) -> OmrStatus;
+
         // bitmap digest (none in the reference)
         pub fn omr_bitmap_ct_count(all_payloads_count: usize, n_ct: *mut u32) -> OmrStatus;
         pub fn omr_encode_bitmap_device(ctx: *mut OmrCtx, d_pv: *const u64, d: usize, global_offset: usize,
@@ -454,6 +482,31 @@ pub fn payload_weights(seed: &[u8; 32], rp: &RetrievalParams) -> Result<Vec<u16>
     check(unsafe {
         omr_payload_weights(seed.as_ptr(), rp.all_payloads_count, l.combination_count, l.cmb_cipher_count,
                             l.cmb_count_per_cipher, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// Indexed payload weights (`omr_indexed_weights_at`, none in the reference): `[n_combos][indices.len()]`,
+/// the weight of combination `first_combo + r` for the global message index `indices[k]`; rows at or
+/// beyond `combination_count` are zero. A function of (seed, combination, index) alone: no table.
+pub fn indexed_weights_at(seed: &[u8; 32], combination_count: u32, first_combo: u32, n_combos: u32,
+                          indices: &[usize]) -> Result<Vec<u16>, OmrError> {
+    let mut out = vec![0u16; n_combos as usize * indices.len()];
+    check(unsafe {
+        omr_indexed_weights_at(seed.as_ptr(), combination_count, first_combo, n_combos, indices.as_ptr(),
+                               indices.len(), out.as_mut_ptr(), 0)
+    })?;
+    Ok(out)
+}
+
+/// The indexed weights in `payload_weights`' layout (`omr_indexed_weights_table`),
+/// `[cmb_cipher_count * cmb_count_per_cipher][all]`.
+pub fn indexed_weights_table(seed: &[u8; 32], rp: &RetrievalParams) -> Result<Vec<u16>, OmrError> {
+    let l = rp.layout;
+    let mut out = vec![0u16; (l.cmb_cipher_count * l.cmb_count_per_cipher) as usize * rp.all_payloads_count];
+    check(unsafe {
+        omr_indexed_weights_table(seed.as_ptr(), rp.all_payloads_count, l.combination_count, l.cmb_cipher_count,
+                                  l.cmb_count_per_cipher, out.as_mut_ptr(), 0)
     })?;
     Ok(out)
 }
@@ -758,6 +811,43 @@ impl GpuDetector {
         Ok(out.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect())
     }
 
+    /// `encode_pertinent_payloads` with indexed weights (`omr_encode_payloads_indexed`): the weights are
+    /// computed in the kernel from `seed`, no board-wide table is drawn or uploaded. The pertinency vector
+    /// covers the messages `global_offset..` of the board.
+    pub fn encode_pertinent_payloads_indexed(&self, pertinency_vector: &[NttRlwe], payloads: &[Payload],
+                                             rp: &RetrievalParams, seed: &[u8; 32],
+                                             global_offset: usize) -> Result<Vec<NttRlwe>, OmrError> {
+        if payloads.len() != pertinency_vector.len() {
+            return Err(OmrError { status: OMR_ERR_INVALID_ARGUMENT, message: "one payload per message".into() });
+        }
+        let pv = NttRlwe::flatten(pertinency_vector);
+        let pay: Vec<u16> = payloads.iter().flat_map(|p| p.iter().copied()).collect();
+        let n_ct = rp.layout.cmb_cipher_count;
+        let mut out = vec![0u64; n_ct as usize * 2 * OMR_N2];
+        check(unsafe {
+            omr_encode_payloads_indexed(self.ctx, pv.as_ptr(), pay.as_ptr(), pertinency_vector.len(), global_offset,
+                                        rp.all_payloads_count, seed.as_ptr(), rp.layout.combination_count, 0, n_ct,
+                                        rp.layout.cmb_count_per_cipher, out.as_mut_ptr())
+        })?;
+        Ok(out.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect())
+    }
+
+    /// The same on device buffers for the ciphertexts `first_ct..first_ct + n_ct`
+    /// (`omr_encode_payloads_indexed_device`): returns once enqueued.
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the detector's GPU in the ABI layouts (`d_out` of
+    /// `n_ct` ciphertexts) and stay valid until the stream has finished.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn encode_payloads_indexed_device(&self, d_pv: *const u64, d_payloads: *const u16, d: usize,
+                                                 global_offset: usize, rp: &RetrievalParams, seed: &[u8; 32],
+                                                 first_ct: u32, n_ct: u32, d_out: *mut u64,
+                                                 hip_stream: *mut c_void) -> Result<(), OmrError> {
+        check(omr_encode_payloads_indexed_device(self.ctx, d_pv, d_payloads, d, global_offset, rp.all_payloads_count,
+                                                 seed.as_ptr(), rp.layout.combination_count, first_ct, n_ct,
+                                                 rp.layout.cmb_count_per_cipher, d_out, hip_stream))
+    }
+
     /// Messages per internal detect chunk (0 = default).
     pub fn set_batch(&self, batch: usize) -> Result<(), OmrError> {
         check(unsafe { omr_ctx_set_batch(self.ctx, batch) })
@@ -851,6 +941,18 @@ impl GpuDetector {
         })?;
         Ok(DigestSession { raw, _detector: self })
     }
+
+    /// `omr_digest_begin_indexed`: the same session with indexed payload weights. It draws and holds no
+    /// weight table; its digest is retrieved with `Retriever::decode_digest_indexed`.
+    pub fn digest_session_indexed(&self, rp: &RetrievalParams, index_seed: u64,
+                                  weight_seed: &[u8; 32]) -> Result<DigestSession<'_>, OmrError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe {
+            omr_digest_begin_indexed(self.ctx, rp.all_payloads_count, rp.pertinent_count, index_seed,
+                                     weight_seed.as_ptr(), std::ptr::null_mut(), &mut raw)
+        })?;
+        Ok(DigestSession { raw, _detector: self })
+    }
 }
 
 impl DigestSession<'_> {
@@ -900,6 +1002,14 @@ impl DigestSession<'_> {
         check(unsafe { omr_digest_read(self.raw, idx.as_mut_ptr(), pay.as_mut_ptr()) })?;
         Ok(Digest { indices: idx.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect(),
                     payloads: pay.chunks_exact(2 * OMR_N2).map(NttRlwe::from_flat).collect() })
+    }
+
+    /// (bytes of device memory the session owns now, the weight table's share of them)
+    /// (`omr_digest_device_bytes`); the share of an indexed session is 0.
+    pub fn device_bytes(&self) -> Result<(usize, usize), OmrError> {
+        let (mut total, mut weights) = (0usize, 0usize);
+        check(unsafe { omr_digest_device_bytes(self.raw, &mut total, &mut weights) })?;
+        Ok((total, weights))
     }
 
     /// Also keep the board's bitmap digest (`omr_digest_enable_bitmap`); before the first update or
@@ -1064,6 +1174,37 @@ impl<'a> Retriever<'a> {
         check(unsafe {
             omr_retrieve_payloads(self.secret.raw, pay.as_ptr(), payloads_digest.len() as u32, rp.all_payloads_count,
                                   rp.layout.combination_count, w.as_ptr(), found_buf.as_ptr(), found_buf.len(), out.as_mut_ptr())
+        })?;
+        let payloads = out
+            .chunks_exact(OMR_PAYLOAD_LEN)
+            .map(|c| {
+                let mut p = [0u16; OMR_PAYLOAD_LEN];
+                p.copy_from_slice(c);
+                p
+            })
+            .collect();
+        Ok((found_buf, payloads))
+    }
+
+    /// `decode_digest` for a digest encoded with indexed weights (`omr_retrieve_payloads_indexed`): the
+    /// system's combination_count x found matrix is computed from `seed`, no board-wide table.
+    pub fn decode_digest_indexed(&self, indices_digest: &[NttRlwe], payloads_digest: &[NttRlwe],
+                                 seed: &[u8; 32]) -> Result<(Vec<usize>, Vec<Payload>), OmrError> {
+        let rp = self.params;
+        let idx = NttRlwe::flatten(indices_digest);
+        let mut found_buf = vec![0usize; rp.pertinent_count.max(1) * 4 + 64];
+        let mut found = 0usize;
+        check(unsafe {
+            omr_retrieve_indices(self.secret.raw, idx.as_ptr(), indices_digest.len() as u32, rp.all_payloads_count,
+                                 rp.pertinent_count, found_buf.as_mut_ptr(), found_buf.len(), &mut found)
+        })?;
+        found_buf.truncate(found.min(found_buf.len()));
+        let pay = NttRlwe::flatten(payloads_digest);
+        let mut out = vec![0u16; found_buf.len() * OMR_PAYLOAD_LEN];
+        check(unsafe {
+            omr_retrieve_payloads_indexed(self.secret.raw, pay.as_ptr(), payloads_digest.len() as u32,
+                                          rp.all_payloads_count, rp.layout.combination_count, seed.as_ptr(),
+                                          found_buf.as_ptr(), found_buf.len(), out.as_mut_ptr())
         })?;
         let payloads = out
             .chunks_exact(OMR_PAYLOAD_LEN)

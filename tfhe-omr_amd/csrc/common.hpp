@@ -76,6 +76,29 @@ OMR_HD void bucket_words(uint64_t seed, uint32_t ct, uint64_t gi, uint32_t out[1
 }
 OMR_HD uint32_t bucket_of(uint32_t word) { return (uint32_t)(((uint64_t)word * BUCKETS) >> 32); }
 
+// Indexed payload weights (include/omr_gpu.h, "Indexed payload weights": none in the reference): weight
+// (j, g) is word g & 15 of the ChaCha12 block with counter g >> 4 and stream id "payw" << 32 | j, scaled
+// to [0, 256] without a rejection step, so that any party evaluates any weight on its own. The key is
+// the 32-byte weight seed as eight little-endian words, passed to kernels by value.
+struct WeightKey {
+  uint32_t k[8];
+};
+inline WeightKey weight_key(const uint8_t seed[32]) {
+  WeightKey key;
+  for (int i = 0; i < 8; ++i)
+    key.k[i] = (uint32_t)seed[4 * i] | ((uint32_t)seed[4 * i + 1] << 8) | ((uint32_t)seed[4 * i + 2] << 16) |
+               ((uint32_t)seed[4 * i + 3] << 24);
+  return key;
+}
+constexpr uint64_t PAYW_STREAM = 0x70617977ull << 32;
+// The 16 weights of combination j for the messages 16 block .. 16 block + 15.
+OMR_HD void indexed_weight_block(const WeightKey &key, uint32_t j, uint64_t block, uint16_t out[16]) {
+  uint32_t w[16];
+  chacha_block(12, key.k, block, PAYW_STREAM | j, w);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) out[i] = (uint16_t)(((uint64_t)w[i] * (uint64_t)P) >> 32);
+}
+
 // Error reporting (thread-local message behind omr_last_error()).
 omr_status set_error(omr_status st, const std::string &msg);
 

@@ -6,6 +6,8 @@
 // per-message terms, so any partition of the board into updates gives the same bits. A session whose
 // bitmap is enabled (omr_digest_enable_bitmap) folds each piece into the bitmap digest as well.
 // omr_digest_read_compact hands the digest out in compact form (compact.hpp) and leaves it as it is.
+// A session from omr_digest_begin_indexed holds no weight table: its payload encode computes the indexed
+// weights (common.hpp) in the kernel; everything else is shared.
 //
 // The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
 // context's detect / encode scratch under the context mutex (ctx.hpp), like any other call.
@@ -27,7 +29,9 @@ struct omr_digest {
   size_t all;
   uint64_t index_seed;
   omr_retrieval_params rp;
-  DevBuf<uint16_t> weights;      // [payload_ct * cmb_count_per_cipher][all]
+  DevBuf<uint16_t> weights;      // [payload_ct * cmb_count_per_cipher][all]; empty in an indexed session
+  bool indexed = false;          // omr_digest_begin_indexed: the weights come from wkey in the kernel
+  WeightKey wkey{};
   DevBuf<uint64_t> digest;       // [index_ct + payload_ct][2][N2], canonical
   DevBuf<uint64_t> pv;           // pertinency ciphertexts of one piece, grown lazily
   DevBuf<uint64_t> merge_stage;  // omr_digest_merge's and omr_digest_merge_bitmap's upload
@@ -82,8 +86,12 @@ omr_status run_piece(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, con
   OMR_TRY(detect_device(c, ca, cb, n, dg->pv, st));
   if (dg->n_bmp) OMR_TRY(encode_bitmap(c, dg->pv, n, offset, dg->all, dg->bitmap, st, true));
   OMR_TRY(encode_indices(c, dg->pv, n, offset, dg->all, dg->index_seed, 0, dg->n_idx(), dg->digest, st, true));
+  uint64_t *pay_digest = dg->digest + (size_t)dg->n_idx() * 2 * N2;
+  if (dg->indexed)
+    return encode_payloads_indexed(c, dg->pv, pay, n, offset, dg->wkey, dg->rp.combination_count, 0, dg->n_pay(),
+                                   dg->rp.cmb_count_per_cipher, pay_digest, st, true);
   return encode_payloads(c, dg->pv, pay, n, offset, dg->all, dg->weights, dg->n_pay(), dg->rp.cmb_count_per_cipher,
-                         dg->digest + (size_t)dg->n_idx() * 2 * N2, st, true);
+                         pay_digest, st, true);
 }
 
 omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, const uint16_t *pay, size_t D,
@@ -125,11 +133,10 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
   return s;
 }
 
-}  // namespace
-
-extern "C" omr_status omr_digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
-                                       const uint8_t weight_seed[32], void *stream, omr_digest **out) {
-  if (!c || !weight_seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_begin: NULL argument");
+// omr_digest_begin and omr_digest_begin_indexed: only the table session draws and uploads weights.
+omr_status digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed, const uint8_t weight_seed[32],
+                        void *stream, omr_digest **out, bool indexed, const char *who) {
+  if (!c || !weight_seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
   *out = nullptr;
   omr_retrieval_params rp;
   omr_status s;
@@ -138,19 +145,36 @@ extern "C" omr_status omr_digest_begin(omr_ctx *c, size_t all, size_t pertinent,
   try {
     std::unique_ptr<omr_digest> dg(new omr_digest(c, (hipStream_t)stream, all, index_seed));
     dg->rp = rp;
-    std::vector<uint16_t> w((size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * all);
-    if ((s = omr_payload_weights(weight_seed, all, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
-                                 w.data())) != OMR_OK)
-      return s;
-    HIP_TRY(dg->weights.upload_sync(w));
+    dg->indexed = indexed;
+    if (indexed) {
+      dg->wkey = weight_key(weight_seed);
+    } else {
+      std::vector<uint16_t> w((size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * all);
+      if ((s = omr_payload_weights(weight_seed, all, rp.combination_count, rp.cmb_cipher_count,
+                                   rp.cmb_count_per_cipher, w.data())) != OMR_OK)
+        return s;
+      HIP_TRY(dg->weights.upload_sync(w));
+    }
     HIP_TRY(dg->digest.alloc(dg->digest_elems()));
     HIP_TRY(hipMemsetAsync(dg->digest, 0, dg->digest_elems() * sizeof(uint64_t), dg->st));
     HIP_TRY(hipStreamSynchronize(dg->st));
     *out = dg.release();
   } catch (const std::bad_alloc &) {
-    return set_error(OMR_ERR_OUT_OF_MEMORY, "omr_digest_begin: host allocation failed");
+    return set_error(OMR_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed");
   }
   return OMR_OK;
+}
+
+}  // namespace
+
+extern "C" omr_status omr_digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
+                                       const uint8_t weight_seed[32], void *stream, omr_digest **out) {
+  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, false, "omr_digest_begin");
+}
+
+extern "C" omr_status omr_digest_begin_indexed(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
+                                               const uint8_t weight_seed[32], void *stream, omr_digest **out) {
+  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, true, "omr_digest_begin_indexed");
 }
 
 extern "C" omr_status omr_digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
@@ -315,6 +339,17 @@ extern "C" omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info)
   info->all_payloads_count = dg->all;
   info->messages = dg->ranges.covered();
   info->pv_capacity_messages = dg->pv.capacity() / (2 * (size_t)N2);
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_device_bytes(omr_digest *dg, size_t *total, size_t *weights) {
+  if (!dg || !total || !weights) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_device_bytes: NULL argument");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  *weights = dg->weights.capacity() * sizeof(uint16_t);
+  *total = *weights + (dg->digest.capacity() + dg->pv.capacity() + dg->merge_stage.capacity() + dg->bitmap.capacity()) *
+                          sizeof(uint64_t) +
+           dg->compact.capacity() * sizeof(uint32_t) +
+           (dg->s_clue_a.capacity() + dg->s_clue_b.capacity() + dg->s_payloads.capacity()) * sizeof(uint16_t);
   return OMR_OK;
 }
 

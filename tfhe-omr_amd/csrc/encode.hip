@@ -1,6 +1,7 @@
 // Encode (detector.rs:223-453): the index and payload encode kernels' launches over the context's
 // partial-sum scratch, their reduction or accumulation, and the four encode entry points; the bitmap
-// digest's kernel (bitmap_kernel.hpp, none in the reference) the same way, with its two entry points.
+// digest's kernel (bitmap_kernel.hpp, none in the reference) the same way, with its two entry points;
+// the payload encode with indexed weights (none in the reference) and the device table of those weights.
 #include <algorithm>
 
 #include "bitmap_kernel.hpp"
@@ -27,6 +28,24 @@ omr_status encode_finish(omr_ctx *c, int chunks, uint32_t n_ct, uint64_t *out, h
   HIP_TRY(hipGetLastError());
   return OMR_OK;
 }
+// The shared body of the index and payload encodes: D messages in chunks of encode_per_wg, `launch`
+// enqueues the encode kernel on grid (chunks, n_ct) over the context's partials, which are then reduced.
+template <typename Launch>
+omr_status encode_chunked(omr_ctx *c, size_t D, uint32_t n_ct, uint64_t *out, hipStream_t st, bool accumulate,
+                          Launch launch) {
+  if (D == 0) {
+    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
+    return OMR_OK;
+  }
+  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
+  const int chunks = (int)((D + per_wg - 1) / per_wg);
+  OMR_TRY(ensure_partial(c, (size_t)n_ct * chunks * 2 * N2));
+  ScratchLease lease;
+  OMR_TRY(lease.acquire(c, st));
+  launch(dim3(chunks, n_ct), per_wg);
+  OMR_TRY(encode_finish(c, chunks, n_ct, out, st, accumulate));
+  return lease.release();
+}
 }  // namespace
 
 omr_status omr::accumulate_partials(const uint64_t *partial, int chunks, uint32_t n_ct, uint64_t *digest,
@@ -41,40 +60,31 @@ omr_status omr::encode_indices(omr_ctx *c, const uint64_t *pv, size_t D, size_t 
                                uint32_t first_ct, uint32_t n_ct, uint64_t *out, hipStream_t st, bool accumulate) {
   omr_retrieval_params rp;
   OMR_TRY(omr_get_retrieval_params(all, 0, &rp));
-  if (D == 0) {
-    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
-    return OMR_OK;
-  }
-  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
-  const int chunks = (int)((D + per_wg - 1) / per_wg);
-  OMR_TRY(ensure_partial(c, (size_t)n_ct * chunks * 2 * N2));
-  ScratchLease lease;
-  OMR_TRY(lease.acquire(c, st));
   EncodeLayout ly{(int)rp.index_slots_per_bucket, (int)rp.slots_per_bucket,
                   (int)rp.slots_per_segment, (int)rp.segment_per_cipher};
-  encode_indices_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, (int)D, offset, ly, seed, first_ct,
-                                                              per_wg, c->tab.tb.tw2, c->scr.partial);
-  OMR_TRY(encode_finish(c, chunks, n_ct, out, st, accumulate));
-  return lease.release();
+  return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
+    encode_indices_kernel<<<grid, ENC_T, 0, st>>>(pv, (int)D, offset, ly, seed, first_ct, per_wg, c->tab.tb.tw2,
+                                                  c->scr.partial);
+  });
 }
 
 omr_status omr::encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, size_t offset,
                                 size_t all, const uint16_t *weights, uint32_t n_ct, uint32_t per_ct, uint64_t *out,
                                 hipStream_t st, bool accumulate) {
-  if (D == 0) {
-    if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), st));
-    return OMR_OK;
-  }
-  const int per_wg = encode_per_wg(D, c->enc_max_chunks);
-  const int chunks = (int)((D + per_wg - 1) / per_wg);
-  OMR_TRY(ensure_partial(c, (size_t)n_ct * chunks * 2 * N2));
-  ScratchLease lease;
-  OMR_TRY(lease.acquire(c, st));
-  encode_payloads_kernel<<<dim3(chunks, n_ct), ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all,
-                                                               weights, (int)per_ct, per_wg,
-                                                               c->tab.tb.tw2, c->scr.partial);
-  OMR_TRY(encode_finish(c, chunks, n_ct, out, st, accumulate));
-  return lease.release();
+  return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
+    encode_payloads_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, weights, (int)per_ct, per_wg,
+                                                   c->tab.tb.tw2, c->scr.partial);
+  });
+}
+
+omr_status omr::encode_payloads_indexed(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                        size_t offset, const WeightKey &key, uint32_t combos, uint32_t first_ct,
+                                        uint32_t n_ct, uint32_t per_ct, uint64_t *out, hipStream_t st,
+                                        bool accumulate) {
+  return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
+    encode_payloads_indexed_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, key, combos, first_ct,
+                                                           (int)per_ct, per_wg, c->tab.tb.tw2, c->scr.partial);
+  });
 }
 
 omr_status omr::encode_bitmap(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all, uint64_t *out,
@@ -173,6 +183,55 @@ extern "C" omr_status omr_encode_payloads(omr_ctx *c, const uint64_t *pv, const 
   OMR_TRY(omr_encode_payloads_device(c, dpv, dpay, D, offset, all, dw, n_ct, per_ct, dout, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_encode_payloads_indexed_device(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
+                                                         size_t D, size_t offset, size_t all, const uint8_t seed[32],
+                                                         uint32_t combos, uint32_t first_ct, uint32_t n_ct,
+                                                         uint32_t per_ct, uint64_t *out, void *stream) {
+  if (!c || !out || !seed || (D && (!pv || !payloads)) || n_ct == 0 || per_ct == 0 ||
+      per_ct * PAYLOAD_LEN > (uint32_t)N2 || offset > all || D > all - offset || D > (size_t)INT32_MAX ||
+      n_ct > 65535)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_indexed_device: bad argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // NULL: HIP's null stream
+  return encode_payloads_indexed(c, pv, payloads, D, offset, weight_key(seed), combos, first_ct, n_ct, per_ct, out,
+                                 (hipStream_t)stream, false);
+}
+
+extern "C" omr_status omr_encode_payloads_indexed(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                                  size_t offset, size_t all, const uint8_t seed[32], uint32_t combos,
+                                                  uint32_t first_ct, uint32_t n_ct, uint32_t per_ct, uint64_t *out) {
+  if (!c || !out || !seed || (D && (!pv || !payloads)) || n_ct == 0)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_indexed");
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<uint64_t> dpv, dout;
+  DevBuf<uint16_t> dpay;
+  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
+  HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
+  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
+  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
+  OMR_TRY(omr_encode_payloads_indexed_device(c, dpv, dpay, D, offset, all, seed, combos, first_ct, n_ct, per_ct, dout,
+                                             c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_indexed_weights_table_device(const uint8_t seed[32], size_t all, uint32_t combos,
+                                                       uint32_t n_ct, uint32_t per_ct, uint16_t *d_out,
+                                                       void *stream) {
+  const uint64_t rows = (uint64_t)n_ct * per_ct, nblk = ((uint64_t)all + 15) >> 4;
+  constexpr unsigned TB = 256;
+  if (!seed || !d_out || all == 0 || rows == 0 || rows < combos || rows > UINT32_MAX ||
+      (rows * nblk + TB - 1) / TB > (uint64_t)INT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_indexed_weights_table_device: bad argument");
+  indexed_weights_table_kernel<<<(unsigned)((rows * nblk + TB - 1) / TB), TB, 0, (hipStream_t)stream>>>(
+      weight_key(seed), all, combos, (uint32_t)rows, d_out);
+  HIP_TRY(hipGetLastError());
   return OMR_OK;
 }
 

@@ -138,6 +138,108 @@ __global__ __launch_bounds__(ENC_T) void encode_payloads_kernel(
   }
 }
 
+// encode_payloads_kernel with indexed weights (common.hpp, indexed_weight_block): the same grid, the
+// same accumulation and the same partials, and no weight table. Ciphertext first_ct + blockIdx.y holds
+// the combinations (first_ct + blockIdx.y) * per_ct + j, j < per_ct; one at or beyond `combos` is padding
+// with weight 0. Per staged block of at most ENC_T messages, thread t < per_ct * nblk computes the one
+// ChaCha12 block of (combination t / nblk, 16-message block t % nblk) into LDS, nblk <= ENC_T / 16 + 1
+// being the 16-message blocks that the staged range of global indices touches.
+constexpr int ENC_W_PER_CT = N2 / PAYLOAD_LEN;        // 3: the most combinations a ciphertext holds
+constexpr int ENC_W_BLOCKS = ENC_T / 16 + 1;          // 9
+static_assert(ENC_W_PER_CT * ENC_W_BLOCKS <= ENC_T, "one thread per staged weight block");
+__global__ __launch_bounds__(ENC_T) void encode_payloads_indexed_kernel(
+    const uint64_t *__restrict__ pv, const uint16_t *__restrict__ payloads, int D, uint64_t offset,
+    WeightKey key, uint32_t combos, uint32_t first_ct, int per_ct, int per_wg,
+    const double *__restrict__ tw, uint64_t *__restrict__ partial) {
+  using M = Mod<2>;
+  constexpr int T = ENC_T, E = ENC_E, N = N2;
+  using NTT = WgNtt<M, T, E>;
+  __shared__ double xch[NTT::LDS_DOUBLES];
+  __shared__ uint16_t wts[ENC_W_PER_CT][ENC_W_BLOCKS * 16];
+  const int tid = threadIdx.x;
+  const int chunk = blockIdx.x, c = blockIdx.y;
+  const int m0 = chunk * per_wg;
+  const int mcount = min(per_wg, D - m0);
+  const uint64_t combo0 = ((uint64_t)first_ct + (uint64_t)c) * (uint64_t)per_ct;
+  double accA[E], accB[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) accA[e] = accB[e] = 0.0;
+  // per_wg may exceed ENC_T (large D): the weights are staged ENC_T messages at a time
+#pragma unroll 1
+  for (int mb = 0; mb < mcount; mb += ENC_T) {
+    const int cnt = min(ENC_T, mcount - mb);
+    const uint64_t g0 = offset + m0 + mb;
+    const uint64_t blk0 = g0 >> 4;
+    const int nblk = (int)(((g0 + cnt - 1) >> 4) - blk0) + 1;
+    const int lane0 = (int)(g0 & 15);  // the first staged message's place in its 16-message block
+    __syncthreads();  // every thread has finished reading the previous block's weights
+    if (tid < per_ct * nblk) {
+      const int j = tid / nblk, b = tid - j * nblk;
+      uint16_t *dst = &wts[j][b * 16];
+      if (combo0 + j < (uint64_t)combos) {
+        indexed_weight_block(key, (uint32_t)(combo0 + j), blk0 + b, dst);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dst[i] = 0;
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int mi = mb; mi < mb + cnt; ++mi) {
+      const int m = m0 + mi;
+      const int wi = lane0 + (mi - mb);
+      double x[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int pos = tid + e * T;
+        const int j = pos / PAYLOAD_LEN;
+        double v = 0.0;
+        if (j < per_ct) {
+          const int l = pos - j * PAYLOAD_LEN;
+          const uint32_t w = wts[j][wi];
+          v = centred_lift(((uint32_t)payloads[(size_t)m * PAYLOAD_LEN + l] * w) % (uint32_t)P);
+        }
+        x[e] = v;
+      }
+      NTT::fwd(x, xch, tw, tid);
+      const uint64_t *pa = pv + (size_t)m * 2 * N + tid * E;
+      const uint64_t *pb = pa + N;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        accA[e] = red<M>(accA[e] + mm<M>(from_u64<M>(pa[e]), x[e]));
+        accB[e] = red<M>(accB[e] + mm<M>(from_u64<M>(pb[e]), x[e]));
+      }
+    }
+  }
+  uint64_t *o = partial + ((size_t)c * gridDim.x + chunk) * 2 * N + tid * E;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    o[e] = to_u64<M>(canon<M>(accA[e]));
+    o[N + e] = to_u64<M>(canon<M>(accB[e]));
+  }
+}
+
+// The indexed weights in omr_payload_weights's layout, out [rows][all] u16: one thread per (row,
+// 16-message block); rows at or beyond `combos` are zero.
+__global__ void indexed_weights_table_kernel(WeightKey key, uint64_t all, uint32_t combos, uint32_t rows,
+                                             uint16_t *__restrict__ out) {
+  const uint64_t nblk = (all + 15) >> 4;
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint64_t)rows * nblk) return;
+  const uint32_t j = (uint32_t)(idx / nblk);
+  const uint64_t b = idx - (uint64_t)j * nblk;
+  uint16_t w[16];
+  if (j < combos) {
+    indexed_weight_block(key, j, b, w);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w[i] = 0;
+  }
+  const uint64_t g0 = b << 4;
+  uint16_t *o = out + (uint64_t)j * all + g0;
+  for (int i = 0; i < 16 && g0 + i < all; ++i) o[i] = w[i];
+}
+
 // out[c][t] = sum_chunk partial[c][chunk][t] mod q2: every partial is canonical (< q2), so the
 // running sum stays canonical with one conditional subtraction per term, for any chunk count.
 __global__ void reduce_partials_kernel(const uint64_t *__restrict__ partial, int chunks,

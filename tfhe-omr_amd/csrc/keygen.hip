@@ -359,3 +359,55 @@ extern "C" omr_status omr_payload_weights(const uint8_t seed[32], size_t all, ui
   memset(out + count, 0, ((size_t)n_ct * per_ct * all - count) * sizeof(uint16_t));
   return OMR_OK;
 }
+
+// Indexed payload weights (include/omr_gpu.h, none in the reference), host side: common.hpp's
+// indexed_weight_block, the statement the encode kernel shares.
+extern "C" omr_status omr_indexed_weights_at(const uint8_t seed[32], uint32_t combos, uint32_t first_combo,
+                                             uint32_t n_combos, const size_t *indices, size_t n_indices,
+                                             uint16_t *out, int nthreads) {
+  if (!seed || (n_indices && !indices) || (n_combos && n_indices && !out))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_indexed_weights_at: NULL argument");
+  if ((uint64_t)first_combo + n_combos > (uint64_t)UINT32_MAX + 1)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_indexed_weights_at: combination beyond 2^32");
+  const WeightKey key = weight_key(seed);
+  parallel_for(n_combos, nthreads, [&](size_t r) {
+    uint16_t *o = out + r * n_indices;
+    const uint64_t j = (uint64_t)first_combo + r;
+    if (j >= combos) {  // a padding combination
+      std::fill(o, o + n_indices, (uint16_t)0);
+      return;
+    }
+    uint16_t w[16];
+    uint64_t have = 0;  // the block in w, valid once k > 0: sorted indices share blocks
+    for (size_t k = 0; k < n_indices; ++k) {
+      const uint64_t g = indices[k];
+      if (k == 0 || (g >> 4) != have) indexed_weight_block(key, (uint32_t)j, have = g >> 4, w);
+      o[k] = w[g & 15];
+    }
+  });
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_indexed_weights_table(const uint8_t seed[32], size_t all, uint32_t combos, uint32_t n_ct,
+                                                uint32_t per_ct, uint16_t *out, int nthreads) {
+  const uint64_t rows = (uint64_t)n_ct * per_ct;
+  if (!seed || !out || all == 0 || rows == 0 || rows < combos)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_indexed_weights_table: bad argument");
+  const WeightKey key = weight_key(seed);
+  constexpr size_t PIECE = 4096;  // 16-message blocks per work item
+  const size_t nblk = (all + 15) / 16, pieces = (nblk + PIECE - 1) / PIECE;
+  parallel_for((size_t)rows * pieces, nthreads, [&](size_t it) {
+    const size_t j = it / pieces, b0 = (it % pieces) * PIECE, b1 = std::min(nblk, b0 + PIECE);
+    uint16_t *o = out + j * all;
+    if (j >= combos) {
+      std::fill(o + b0 * 16, o + std::min(all, b1 * 16), (uint16_t)0);
+      return;
+    }
+    uint16_t w[16];
+    for (size_t b = b0; b < b1; ++b) {
+      indexed_weight_block(key, (uint32_t)j, b, w);
+      for (size_t i = 0; i < 16 && b * 16 + i < all; ++i) o[b * 16 + i] = w[i];
+    }
+  });
+  return OMR_OK;
+}

@@ -124,13 +124,15 @@ extern "C" omr_status omr_retrieve_indices(const omr_secret_key_pack *sk, const 
   return OMR_OK;
 }
 
-extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const uint64_t *pay_cts,
-                                            uint32_t n_ct, size_t all_payloads_count,
-                                            uint32_t combination_count, const uint16_t *weights,
-                                            const size_t *indices,
-                                            size_t n_indices, uint16_t *payloads) {
-  if (!sk || !pay_cts || !weights || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: NULL argument");
+namespace {
+
+// The body of omr_retrieve_payloads and omr_retrieve_payloads_indexed after their NULL checks: they
+// differ in where the system's matrix comes from. fill(rows, m) writes m[j][k], the weight of combination
+// j for the k-th index, and returns a status.
+template <typename Fill>
+omr_status retrieve_payloads_body(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
+                                  size_t all_payloads_count, uint32_t combination_count, const size_t *indices,
+                                  size_t n_indices, uint16_t *payloads, const std::string &who, Fill fill) {
   omr_retrieval_params rp;
   omr_status st = omr_get_retrieval_params(all_payloads_count, n_indices, &rp);
   if (st != OMR_OK) return st;
@@ -138,12 +140,12 @@ extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const
                per = rp.cmb_count_per_cipher;
   if (n_indices == 0) return OMR_OK;
   if ((size_t)n_ct * per < rows)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: too few payload ciphertexts");
+    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": too few payload ciphertexts");
   if (rows < cols)  // matrix.rs:171 asserts num_rows >= num_cols
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: fewer combinations than indices");
+    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": fewer combinations than indices");
   for (size_t i = 0; i < n_indices; ++i)
     if (indices[i] >= all_payloads_count)
-      return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: index out of range");
+      return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": index out of range");
   // decode_combined_payloads: combination j lives in ciphertext j / per, slots (j % per) * 612..
   std::vector<std::vector<uint32_t>> rhs(rows, std::vector<uint32_t>(PAYLOAD_LEN));
   std::vector<uint32_t> dec((size_t)n_ct * N2);
@@ -152,8 +154,7 @@ extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const
     for (int b = 0; b < PAYLOAD_LEN; ++b) rhs[j][b] = dec[(j / per) * N2 + (j % per) * PAYLOAD_LEN + b];
   // matrix[j][k] = weight of combination j for the k-th retrieved index (retriever.rs:220-238)
   std::vector<std::vector<uint32_t>> m(rows, std::vector<uint32_t>(cols));
-  for (size_t j = 0; j < rows; ++j)
-    for (size_t k = 0; k < cols; ++k) m[j][k] = weights[j * all_payloads_count + indices[k]] % P;
+  if ((st = fill(rows, m)) != OMR_OK) return st;
   auto inv = [](uint32_t v) {  // v^(p-2) mod p
     uint32_t r = 1, b = v % P;
     for (uint32_t e = P - 2; e; e >>= 1, b = b * b % P)
@@ -193,6 +194,44 @@ extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const
   for (size_t k = 0; k < cols; ++k)
     for (int b = 0; b < PAYLOAD_LEN; ++b) payloads[k * PAYLOAD_LEN + b] = (uint16_t)rhs[k][b];
   return OMR_OK;
+}
+
+}  // namespace
+
+extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const uint64_t *pay_cts,
+                                            uint32_t n_ct, size_t all_payloads_count,
+                                            uint32_t combination_count, const uint16_t *weights,
+                                            const size_t *indices,
+                                            size_t n_indices, uint16_t *payloads) {
+  if (!sk || !pay_cts || !weights || (n_indices && (!indices || !payloads)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: NULL argument");
+  return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
+                                "omr_retrieve_payloads", [&](size_t rows, std::vector<std::vector<uint32_t>> &m) {
+                                  for (size_t j = 0; j < rows; ++j)
+                                    for (size_t k = 0; k < n_indices; ++k)
+                                      m[j][k] = weights[j * all_payloads_count + indices[k]] % P;
+                                  return OMR_OK;
+                                });
+}
+
+extern "C" omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *sk, const uint64_t *pay_cts,
+                                                    uint32_t n_ct, size_t all_payloads_count,
+                                                    uint32_t combination_count, const uint8_t weight_seed[32],
+                                                    const size_t *indices, size_t n_indices, uint16_t *payloads) {
+  if (!sk || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_indexed: NULL argument");
+  return retrieve_payloads_body(
+      sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
+      "omr_retrieve_payloads_indexed", [&](size_t rows, std::vector<std::vector<uint32_t>> &m) {
+        // every row is a real combination of the board: rows = combination_count (or its default)
+        std::vector<uint16_t> w(rows * n_indices);
+        const omr_status s = omr_indexed_weights_at(weight_seed, (uint32_t)rows, 0, (uint32_t)rows, indices,
+                                                    n_indices, w.data(), 0);
+        if (s != OMR_OK) return s;
+        for (size_t j = 0; j < rows; ++j)
+          for (size_t k = 0; k < n_indices; ++k) m[j][k] = w[j * n_indices + k] % P;
+        return OMR_OK;
+      });
 }
 
 extern "C" omr_status omr_bitmap_ct_count(size_t all, uint32_t *n_ct) {

@@ -5,7 +5,7 @@
 // indices and their payloads come back.
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
-//           [--compact BITS] [--audit-key] [--host-only]
+//           [--compact BITS] [--audit-key] [--indexed-weights] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -28,6 +28,10 @@
 // --audit-key audits the detection key it generated against the recipient's secret on the GPU before the
 // detector is created (omr_audit_key, or omr_audit_key_seeded with --seeded; include/omr_gpu.h, "Key audit"):
 // a row whose noise lies outside the generators' support, in any component, fails the run.
+// --indexed-weights uses indexed payload weights on both sides (include/omr_gpu.h, "Indexed payload weights"):
+// the detector encodes with omr_encode_payloads_indexed (or a session from omr_digest_begin_indexed) and the
+// recipient solves with omr_retrieve_payloads_indexed; nobody draws the board-wide weight table. With
+// --host-only it checks omr_indexed_weights_at against omr_indexed_weights_table on the pertinent set.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -69,7 +73,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false, bitmap = false, seeded = false, audit_key = false;
+  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false;
   int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -82,10 +86,11 @@ int main(int argc, char **argv) {
     else if (a == "--seeded") seeded = true;
     else if (a == "--compact" && i + 1 < argc) compact_bits = std::atoi(argv[++i]);
     else if (a == "--audit-key") audit_key = true;
+    else if (a == "--indexed-weights") indexed = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--seeded] [--compact BITS] [--audit-key] [--host-only]\n",
+                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -164,9 +169,11 @@ int main(int argc, char **argv) {
   CHECK(omr_get_retrieval_params(D, pert_count, &rp));
   uint8_t wseed[32];
   for (int i = 0; i < 32; ++i) wseed[i] = (uint8_t)(rng() & 0xff);
-  std::vector<uint16_t> weights((size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * D);
-  CHECK(omr_payload_weights(wseed, D, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
-                            weights.data()));
+  // the board-wide table of the reference's weights; with --indexed-weights nobody needs one
+  std::vector<uint16_t> weights(indexed ? 0 : (size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * D);
+  if (!indexed)
+    CHECK(omr_payload_weights(wseed, D, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
+                              weights.data()));
   std::printf("retrieval params: %u index ct, %u payload ct (%u combinations)\n",
               rp.max_encode_indices_cipher_count, rp.cmb_cipher_count, rp.combination_count);
   uint32_t n_bmp = 0;
@@ -186,6 +193,25 @@ int main(int argc, char **argv) {
       return 1;
     }
     std::printf("host-only: bitmap layout OK (%u bitmap ct, %zu indices)\n", n_bmp, nback);
+  }
+  if (host_only && indexed) {
+    // the recipient's submatrix against the table layout: the same function of (seed, combination, index)
+    const size_t rows = (size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher;
+    std::vector<uint16_t> table(rows * D), at(rows * pert_count);
+    CHECK(omr_indexed_weights_table(wseed, D, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
+                                    table.data(), 0));
+    CHECK(omr_indexed_weights_at(wseed, rp.combination_count, 0, (uint32_t)rows, pert.data(), pert_count, at.data(), 0));
+    bool ok = true;
+    for (size_t j = 0; j < rows; ++j)
+      for (size_t k = 0; k < pert_count; ++k) {
+        const uint16_t w = at[j * pert_count + k];
+        ok = ok && w == table[j * D + pert[k]] && w <= 256 && (j < rp.combination_count || w == 0);
+      }
+    if (!ok) {
+      std::printf("Fail: omr_indexed_weights_at differs from omr_indexed_weights_table\nFAILED\n");
+      return 1;
+    }
+    std::printf("host-only: indexed weights OK (%zu x %zu submatrix of a %zu x %zu table)\n", rows, pert_count, rows, D);
   }
   if (host_only) {
     std::printf("host-only: keys, clues, weights and parameters OK\n");
@@ -248,7 +274,8 @@ int main(int argc, char **argv) {
     // the same flow inside the library, piece by piece (omr_digest_*): detect + both encoders
     t = clk::now();
     omr_digest *dg = nullptr;
-    CHECK(omr_digest_begin(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
+    if (indexed) CHECK(omr_digest_begin_indexed(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
+    else CHECK(omr_digest_begin(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
     if (bitmap) CHECK(omr_digest_enable_bitmap(dg));
     for (size_t off = 0; off < D; off += session_piece) {
       const size_t n = std::min(session_piece, D - off);
@@ -295,9 +322,13 @@ int main(int argc, char **argv) {
       CHECK(omr_encode_indices(ctx, pv.data(), D, 0, D, seed + 3, c, &idx_ct[(size_t)c * 2 * N2]));
     std::printf("encode indices time: %.3f s\n", secs(t));
     t = clk::now();
-    CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
-                              rp.cmb_count_per_cipher, pay_ct.data()));
-    std::printf("encode pertinent payloads time: %.3f s\n", secs(t));
+    if (indexed)
+      CHECK(omr_encode_payloads_indexed(ctx, pv.data(), payloads.data(), D, 0, D, wseed, rp.combination_count, 0, n_pay,
+                                        rp.cmb_count_per_cipher, pay_ct.data()));
+    else
+      CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
+                                rp.cmb_count_per_cipher, pay_ct.data()));
+    std::printf("encode pertinent payloads time: %.3f s%s\n", secs(t), indexed ? " (indexed weights)" : "");
     if (bitmap) {
       t = clk::now();
       CHECK(omr_encode_bitmap(ctx, pv.data(), D, 0, D, bmp_ct.data()));
@@ -375,8 +406,12 @@ int main(int argc, char **argv) {
   }
   found.resize(std::min(nfound, found.size()));
   std::vector<uint16_t> solved(found.size() * PAYLOAD);
-  CHECK(omr_retrieve_payloads(pa, pay_ct.data(), n_pay, D, rp.combination_count, weights.data(), found.data(), found.size(),
-                              solved.data()));
+  if (indexed)
+    CHECK(omr_retrieve_payloads_indexed(pa, pay_ct.data(), n_pay, D, rp.combination_count, wseed, found.data(),
+                                        found.size(), solved.data()));
+  else
+    CHECK(omr_retrieve_payloads(pa, pay_ct.data(), n_pay, D, rp.combination_count, weights.data(), found.data(),
+                                found.size(), solved.data()));
   std::printf("decode time: %.3f s\n", secs(t));
 
   int fails = (found == pert ? 0 : 1) + audit_fails + compact_fails;

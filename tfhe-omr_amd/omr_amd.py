@@ -116,6 +116,23 @@ EXPORTS = {
     "omr_ctx_create_seeded": (C.c_int, [C.POINTER(_SeededKeyView), C.c_int, C.POINTER(C.c_void_p)]),
     "omr_get_retrieval_params": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(_RetrievalParams)]),
     "omr_payload_weights": (C.c_int, [_u8p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u16p]),
+    "omr_indexed_weights_at": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_int]),
+    "omr_indexed_weights_table": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                            C.c_int]),
+    "omr_indexed_weights_table_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.c_void_p, C.c_void_p]),
+    "omr_encode_payloads_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "omr_encode_payloads_indexed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                     C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_uint32, C.c_void_p, C.c_void_p]),
+    "omr_digest_begin_indexed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_void_p)]),
+    "omr_digest_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "omr_retrieve_payloads_indexed": (C.c_int, [C.c_void_p, _u64p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                np.ctypeslib.ndpointer(dtype=np.uintp, flags="C_CONTIGUOUS"),
+                                                C.c_size_t, _u16p]),
     "omr_ctx_create": (C.c_int, [C.POINTER(_KeyView), C.c_int, C.POINTER(C.c_void_p)]),
     "omr_ctx_destroy": (None, [C.c_void_p]),
     "omr_ctx_set_batch": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -269,6 +286,48 @@ def payload_weights(seed: bytes, rp: RetrievalParams) -> np.ndarray:
                                      rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher, out),
            "omr_payload_weights")
     return out
+
+
+def _seed_ptr(seed):
+    """The address of a 32-byte weight seed (and the array that keeps it alive); None passes NULL."""
+    if seed is None:
+        return None, None
+    a = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+    if a.size != 32:
+        raise OmrError("weight seed must be 32 bytes")
+    return a.ctypes.data, a
+
+
+def indexed_weights_at(seed: bytes, combination_count: int, indices, first_combo: int = 0, n_combos: int = None,
+                       nthreads: int = 0) -> np.ndarray:
+    """omr_indexed_weights_at: u16 [n_combos][len(indices)], w(first_combo + r, indices[k]) of the indexed
+    payload weights (include/omr_gpu.h); rows at or beyond combination_count are zero. n_combos defaults to
+    the combinations from first_combo up to combination_count (the recipient's matrix for first_combo = 0)."""
+    idx = np.ascontiguousarray(indices, dtype=np.uintp).reshape(-1)
+    n = max(combination_count - first_combo, 0) if n_combos is None else n_combos
+    out = np.empty((n, idx.size), np.uint16)
+    ptr, _keep = _seed_ptr(seed)
+    _check(lib().omr_indexed_weights_at(ptr, combination_count, first_combo, n, idx.ctypes.data, idx.size,
+                                        out.ctypes.data, nthreads), "omr_indexed_weights_at")
+    return out
+
+
+def indexed_weights_table(seed: bytes, rp: RetrievalParams, nthreads: int = 0) -> np.ndarray:
+    """omr_indexed_weights_table: the indexed weights in payload_weights' layout, [n_ct*per_ct][all] u16 flat."""
+    out = np.empty(rp.cmb_cipher_count * rp.cmb_count_per_cipher * rp.all_payloads_count, dtype=np.uint16)
+    ptr, _keep = _seed_ptr(seed)
+    _check(lib().omr_indexed_weights_table(ptr, rp.all_payloads_count, rp.combination_count, rp.cmb_cipher_count,
+                                           rp.cmb_count_per_cipher, out.ctypes.data, nthreads),
+           "omr_indexed_weights_table")
+    return out
+
+
+def indexed_weights_table_device(seed: bytes, all_payloads_count: int, combination_count: int, n_ct: int, per_ct: int,
+                                 d_out: int, stream: int = 0) -> None:
+    """omr_indexed_weights_table_device: the same table into a device buffer u16 [n_ct*per_ct][all]."""
+    ptr, _keep = _seed_ptr(seed)
+    _check(lib().omr_indexed_weights_table_device(ptr, all_payloads_count, combination_count, n_ct, per_ct,
+                                                  d_out or None, stream or None), "omr_indexed_weights_table_device")
 
 
 @dataclass
@@ -576,6 +635,18 @@ class Retriever:
                                            len(idx), out.reshape(-1)), "omr_retrieve_payloads")
         return out
 
+    def decode_combined_payloads_and_solve_indexed(self, pay_cts, seed: bytes, indices) -> np.ndarray:
+        """omr_retrieve_payloads_indexed: the same solve, the matrix from the indexed weights of `seed`."""
+        rp = self.params
+        cts = np.ascontiguousarray(pay_cts, dtype=np.uint64).reshape(-1, 2, N2)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        out = np.zeros((len(idx), PAYLOAD_LENGTH), np.uint16)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_retrieve_payloads_indexed(self._sk._h, cts.reshape(-1), cts.shape[0], rp.all_payloads_count,
+                                                   rp.combination_count, ptr, idx, len(idx), out.reshape(-1)),
+               "omr_retrieve_payloads_indexed")
+        return out
+
     def decode_bitmap(self, bitmap_cts, cap: int = 1024) -> list[int]:
         """omr_retrieve_bitmap: every pertinent global index of the board, increasing, from its bitmap
         digest u64 [bitmap_ct_count(all)][2][2048]; needs no pertinent count."""
@@ -584,10 +655,13 @@ class Retriever:
             self._sk._h, cts.reshape(-1), cts.shape[0], self.params.all_payloads_count, i, c, f),
             "omr_retrieve_bitmap", cap)
 
-    def decode_digest(self, idx_cts, pay_cts, seed: bytes):
+    def decode_digest(self, idx_cts, pay_cts, seed: bytes, indexed: bool = False):
         """Retriever::decode_digest: sorted pertinent indices and their payloads (mod 257); the
-        weights and the system's rows follow the board's RetrievalParams (retriever.rs:196, :215-239)."""
+        weights and the system's rows follow the board's RetrievalParams (retriever.rs:196, :215-239).
+        indexed=True: the digest was encoded with indexed weights; no board-wide table is drawn."""
         indices = self.decode_pertinent_indices(idx_cts)
+        if indexed:
+            return indices, self.decode_combined_payloads_and_solve_indexed(pay_cts, seed, indices)
         weights = payload_weights(seed, self.params)
         return indices, self.decode_combined_payloads_and_solve(pay_cts, weights, indices)
 
@@ -1081,6 +1155,22 @@ class Detector:
                                          rp.all_payloads_count, w, n_ct, per, out.reshape(-1)), "omr_encode_payloads")
         return out
 
+    def encode_pertinent_payloads_indexed(self, pertinency_vector, payloads, seed: bytes, rp: RetrievalParams,
+                                          global_offset: int = 0, first_ct: int = 0, n_ct: int = None) -> np.ndarray:
+        """omr_encode_payloads_indexed: encode_pertinent_payloads with indexed weights (no table), the
+        ciphertexts [first_ct, first_ct + n_ct) of the digest (default: all of rp's)."""
+        pv = np.ascontiguousarray(pertinency_vector, dtype=np.uint64)
+        pay = np.ascontiguousarray(payloads, dtype=np.uint16)
+        D = pv.shape[0]
+        n = rp.cmb_cipher_count - first_ct if n_ct is None else n_ct
+        out = np.empty((max(n, 0), 2, N2), np.uint64)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_encode_payloads_indexed(self._h, pv.ctypes.data, pay.ctypes.data, D, global_offset,
+                                                 rp.all_payloads_count, ptr, rp.combination_count, first_ct, n,
+                                                 rp.cmb_count_per_cipher, out.ctypes.data),
+               "omr_encode_payloads_indexed")
+        return out
+
     def encode_bitmap(self, pertinency_vector, all_payloads_count: int, global_offset: int = 0) -> np.ndarray:
         """omr_encode_bitmap (none in the reference): the board's bitmap digest u64
         [bitmap_ct_count(all)][2][2048] over the messages global_offset.. of the pertinency vector."""
@@ -1108,6 +1198,16 @@ class Detector:
                                                 d_weights, n_ct, per_ct, d_out, stream or None),
                "omr_encode_payloads_device")
 
+    def encode_pertinent_payloads_indexed_device(self, d_pv: int, d_payloads: int, D: int, global_offset: int,
+                                                 all_payloads_count: int, seed: bytes, combination_count: int,
+                                                 first_ct: int, n_ct: int, per_ct: int, d_out: int,
+                                                 stream: int = 0) -> None:
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_encode_payloads_indexed_device(self._h, d_pv or None, d_payloads or None, D, global_offset,
+                                                        all_payloads_count, ptr, combination_count, first_ct, n_ct,
+                                                        per_ct, d_out or None, stream or None),
+               "omr_encode_payloads_indexed_device")
+
     # compact ciphertexts (include/omr_gpu.h, "Compact ciphertexts"): the server side
     def compact_cts(self, cts, bits: int) -> np.ndarray:
         """omr_compact_cts: host NttRlweCiphertexts u64 [n][2][2048] -> u8 [n][512 * bits] through the device."""
@@ -1128,10 +1228,11 @@ class Detector:
         _check(lib().omr_ctx_set_compact_staging(self._h, max_ciphertexts), "omr_ctx_set_compact_staging")
 
     def digest_session(self, all_payloads_count: int, pertinent_count: int, index_seed: int, weight_seed: bytes,
-                       stream: int = 0) -> "DigestSession":
+                       stream: int = 0, indexed: bool = False) -> "DigestSession":
         """A digest session on this detector (omr_digest_begin): detect + encode a board piece by
-        piece without holding its pertinency vector. A context manager."""
-        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream)
+        piece without holding its pertinency vector. A context manager. indexed=True: a session with
+        indexed payload weights (omr_digest_begin_indexed), which holds no weight table."""
+        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream, indexed)
 
     # ---- stage entry points (benches/two_level_bs.rs) ----
     def first_level(self, clue_a, clue_b) -> np.ndarray:
@@ -1202,13 +1303,15 @@ class DigestSession:
     device and at most one detect chunk of pertinency ciphertexts is ever allocated."""
 
     def __init__(self, detector: "Detector", all_payloads_count: int, pertinent_count: int, index_seed: int,
-                 weight_seed: bytes, stream: int = 0):
+                 weight_seed: bytes, stream: int = 0, indexed: bool = False):
         seed = np.frombuffer(bytes(weight_seed), dtype=np.uint8).copy()
         if seed.size != 32:
             raise OmrError("weight_seed must be 32 bytes")
         h = C.c_void_p()
-        _check(lib().omr_digest_begin(detector.handle, all_payloads_count, pertinent_count, index_seed,
-                                      seed.ctypes.data, stream or None, C.byref(h)), "omr_digest_begin")
+        begin, what = ((lib().omr_digest_begin_indexed, "omr_digest_begin_indexed") if indexed else
+                       (lib().omr_digest_begin, "omr_digest_begin"))
+        _check(begin(detector.handle, all_payloads_count, pertinent_count, index_seed, seed.ctypes.data,
+                     stream or None, C.byref(h)), what)
         self._h = h
         self._destroy = lib().omr_digest_destroy
         self._detector = detector  # the context outlives the session
@@ -1285,6 +1388,12 @@ class DigestSession:
         t = _DigestInfo()
         _check(lib().omr_digest_get_info(self._h, C.byref(t)), "omr_digest_get_info")
         return {n: getattr(t, n) for n, _ in _DigestInfo._fields_}
+
+    def device_bytes(self) -> dict:
+        """omr_digest_device_bytes: the device memory the session owns now, and the weights' share of it."""
+        total, weights = C.c_size_t(), C.c_size_t()
+        _check(lib().omr_digest_device_bytes(self._h, C.byref(total), C.byref(weights)), "omr_digest_device_bytes")
+        return {"total": total.value, "weights": weights.value}
 
     def close(self):
         if getattr(self, "_h", None):
