@@ -814,6 +814,13 @@ omr_status omr_key_validate_seeded_device(const omr_seeded_key_view *key, int de
 /* First level (detector.rs:533-597) for D messages: out u32 [D][671] (a[670], b mod 4096). */
 omr_status omr_first_level(omr_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,
                            size_t D, uint32_t *lwe_int);
+/* Test entry: the first level after its rotations (sum of the seven extracted LWEs mod q1, key switch,
+ * modulus switch, body offset; detector.rs:556-594) on caller-supplied extracted LWEs. ext u32
+ * [n][7][1025]: per message and clue the mask a[1024] then the body, in the layout the rotations write
+ * (coefficient-0 extraction: a'[0] = a[0], a'[j] = -a[1024 - j]); out u32 [n][671] as omr_first_level's.
+ * The same kernel selection as omr_first_level (n, the latency threshold). n <= the batch size; a word
+ * >= q1 is OMR_ERR_INVALID_ARGUMENT, checked on the host before anything is enqueued. */
+omr_status omr_sum_key_switch(omr_ctx *ctx, const uint32_t *ext, size_t n, uint32_t *lwe_int);
 /* One level-1 blind rotation per LWE (a u16 [n][512], b u16 [n]): out u64 [n][2][1024]. */
 omr_status omr_blind_rotate_level1(omr_ctx *ctx, const uint16_t *lwe_a, const uint16_t *lwe_b,
                                    size_t n, uint64_t *out);

@@ -426,23 +426,10 @@ void oref_br1_from(const oref_ctx *ctx, const uint16_t *lwe_a, const uint64_t *a
   blind_rotate(1, ctx->lut1, a, 0, OREF_N0, ctx->bsk1, acc0, rlwe_out);
 }
 
-/* first_level_bootstrapping, detector.rs:533-597 */
-void oref_first_level(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,
-                      uint32_t *lwe_int) {
+/* The tail of first_level_bootstrapping from the key switch onward (detector.rs:560-594) on the
+ * extracted LWE (ea, eb) mod q1, canonical: oref_first_level and oref_sum_key_switch end here. */
+static void key_switch_mod_switch(const oref_ctx *ctx, const uint64_t *ea, uint64_t eb, uint32_t *lwe_int) {
   const uint64_t q = OREF_Q1;
-  uint64_t sum[2 * OREF_N1], r[2 * OREF_N1];
-  memset(sum, 0, sizeof(sum));
-  for (int c = 0; c < OREF_CLUES; ++c) {
-    uint16_t la[OREF_N0], lb;
-    oref_extract_clue(clue_a, clue_b, c, la, &lb);
-    oref_br1(ctx, la, lb, r);
-    for (int j = 0; j < 2 * OREF_N1; ++j) sum[j] = addmod(sum[j], r[j], q); /* :556 */
-  }
-  /* extract_lwe_locally (coefficient 0), :561 */
-  uint64_t ea[OREF_N1];
-  ea[0] = sum[0];
-  for (int j = 1; j < OREF_N1; ++j) ea[j] = negmod(sum[OREF_N1 - j], q);
-  uint64_t eb = sum[OREF_N1];
   /* NonPowOf2LweKeySwitchingKey::key_switch, :560-563 */
   uint64_t ka[OREF_NI];
   memset(ka, 0, sizeof(ka));
@@ -459,6 +446,36 @@ void oref_first_level(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_
   for (int c = 0; c < OREF_NI; ++c) lwe_int[c] = (uint32_t)oref_modswitch_q1_to_qi(ka[c]);
   lwe_int[OREF_NI] =
       (uint32_t)((oref_modswitch_q1_to_qi(kb) + OREF_CLUES * (OREF_QI / OREF_TI)) % OREF_QI);
+}
+
+/* first_level_bootstrapping, detector.rs:533-597 */
+void oref_first_level(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,
+                      uint32_t *lwe_int) {
+  const uint64_t q = OREF_Q1;
+  uint64_t sum[2 * OREF_N1], r[2 * OREF_N1];
+  memset(sum, 0, sizeof(sum));
+  for (int c = 0; c < OREF_CLUES; ++c) {
+    uint16_t la[OREF_N0], lb;
+    oref_extract_clue(clue_a, clue_b, c, la, &lb);
+    oref_br1(ctx, la, lb, r);
+    for (int j = 0; j < 2 * OREF_N1; ++j) sum[j] = addmod(sum[j], r[j], q); /* :556 */
+  }
+  /* extract_lwe_locally (coefficient 0), :561 */
+  uint64_t ea[OREF_N1];
+  ea[0] = sum[0];
+  for (int j = 1; j < OREF_N1; ++j) ea[j] = negmod(sum[OREF_N1 - j], q);
+  key_switch_mod_switch(ctx, ea, sum[OREF_N1], lwe_int);
+}
+
+/* The first level after its rotations, on the seven extracted LWEs of one message (ext u32 [7][1025]:
+ * mask then body, canonical): their sum mod q1 (:556), then the key switch, modulus switch and offset. */
+void oref_sum_key_switch(const oref_ctx *ctx, const uint32_t *ext, uint32_t *lwe_int) {
+  const uint64_t q = OREF_Q1;
+  uint64_t e[OREF_N1 + 1];
+  memset(e, 0, sizeof(e));
+  for (int c = 0; c < OREF_CLUES; ++c)
+    for (int j = 0; j <= OREF_N1; ++j) e[j] = addmod(e[j], ext[(size_t)c * (OREF_N1 + 1) + j], q);
+  key_switch_mod_switch(ctx, e, e[OREF_N1], lwe_int);
 }
 
 /* second_level_bootstrapping, detector.rs:599-624 (4096 == 2*N2: no modulus switch) */

@@ -97,6 +97,10 @@ void oref_extract_clue(const uint16_t *clue_a, const uint16_t *clue_b, int i, ui
 void oref_br1(const oref_ctx *ctx, const uint16_t *lwe_a, uint16_t lwe_b, uint64_t *rlwe_out);
 void oref_first_level(const oref_ctx *ctx, const uint16_t *clue_a, const uint16_t *clue_b,
                       uint32_t *lwe_int /* 671: a[670], b; mod 4096 */);
+/* oref_first_level after its rotations: the sum of the seven extracted LWEs of one message mod q1
+ * (ext u32 [7][1025]: a[1024] then b, canonical; a'[0] = a[0], a'[j] = -a[N1 - j] of oref_br1's output),
+ * then the key switch, the modulus switch and the body offset. */
+void oref_sum_key_switch(const oref_ctx *ctx, const uint32_t *ext, uint32_t *lwe_int /* 671 */);
 void oref_br2(const oref_ctx *ctx, const uint32_t *lwe_int, uint64_t *rlwe_out);
 /* The blind rotations from a supplied initial accumulator acc0 (u64 [2][N], canonical, coefficient
  * domain: the outputs' layout) instead of (0, X^{-b} * LUT); the LWE body is unused. */

@@ -376,6 +376,7 @@ pub mod ffi {
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
                                lwe_int: *mut u32) -> OmrStatus;
+        pub fn omr_sum_key_switch(ctx: *mut OmrCtx, ext: *const u32, n: usize, lwe_int: *mut u32) -> OmrStatus;
         pub fn omr_blind_rotate_level1(ctx: *mut OmrCtx, lwe_a: *const u16, lwe_b: *const u16, n: usize,
                                        out: *mut u64) -> OmrStatus;
         pub fn omr_fft1_mul(ctx: *mut OmrCtx, a: *const u32, k: *const u32, n: usize, out: *mut u64) -> OmrStatus;

@@ -46,6 +46,7 @@ def lib():
         "oref_extract_clue": (None, [_u16p, _u16p, C.c_int, _u16p, _u16p]),
         "oref_br1": (None, [C.c_void_p, _u16p, C.c_uint16, _u64p]),
         "oref_first_level": (None, [C.c_void_p, _u16p, _u16p, _u32p]),
+        "oref_sum_key_switch": (None, [C.c_void_p, _u32p, _u32p]),
         "oref_br2": (None, [C.c_void_p, _u32p, _u64p]),
         "oref_br1_from": (None, [C.c_void_p, _u16p, _u64p, _u64p]),
         "oref_br2_from": (None, [C.c_void_p, _u32p, _u64p, _u64p]),
@@ -99,6 +100,14 @@ class OracleDetector:
         out = np.zeros(671, dtype=np.uint32)
         lib().oref_first_level(self._h, np.ascontiguousarray(clue_a, dtype=np.uint16),
                                np.ascontiguousarray(clue_b, dtype=np.uint16), out)
+        return out
+
+    def sum_key_switch(self, ext):
+        """first_level after its rotations, on the seven extracted LWEs of one message (u32 [7][1025])."""
+        ext = np.ascontiguousarray(ext, dtype=np.uint32)
+        assert ext.shape == (7, 1025)
+        out = np.zeros(671, dtype=np.uint32)
+        lib().oref_sum_key_switch(self._h, ext.reshape(-1), out)
         return out
 
     def br2(self, lwe_int):

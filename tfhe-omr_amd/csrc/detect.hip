@@ -311,6 +311,14 @@ omr_status launch_trace_only(omr_ctx *c, size_t n, uint64_t *io, uint64_t *saved
   return guard_end(c, 1, st);
 }
 
+// The first level after its rotations: the seven extracted LWEs of each of B messages in scr.ext ->
+// sum7 -> key switch into scr.lwe_int (launch_first_level, and the stage entry omr_sum_key_switch).
+omr_status launch_sum_ks(omr_ctx *c, int B, hipStream_t st) {
+  const size_t n7 = (size_t)B * (N1 + 1);
+  sum7_kernel<<<(unsigned)((n7 + 255) / 256), 256, 0, st>>>(c->scr.ext, c->scr.lwe1t, B);
+  return launch_ks(c, B, c->scr.lwe_int, st);
+}
+
 // The first level of B messages: br1 (7 rotations per message) -> sum7 -> key switch into
 // scr.lwe_int. With ev (detect_device's stage events) ev[1] is recorded after br1, ev[2] after the
 // key switch.
@@ -318,9 +326,7 @@ omr_status launch_first_level(omr_ctx *c, int B, const uint16_t *ca, const uint1
                               hipEvent_t *ev = nullptr) {
   OMR_TRY(launch_br1(c, (size_t)B * CLUES, ca, cb, nullptr, nullptr, c->scr.ext, nullptr, 0, st, (size_t)B));
   if (ev) HIP_TRY(hipEventRecord(ev[1], st));
-  const size_t n7 = (size_t)B * (N1 + 1);
-  sum7_kernel<<<(unsigned)((n7 + 255) / 256), 256, 0, st>>>(c->scr.ext, c->scr.lwe1t, B);
-  OMR_TRY(launch_ks(c, B, c->scr.lwe_int, st));
+  OMR_TRY(launch_sum_ks(c, B, st));
   if (ev) HIP_TRY(hipEventRecord(ev[2], st));
   return OMR_OK;
 }
@@ -486,6 +492,32 @@ extern "C" omr_status omr_first_level(omr_ctx *c, const uint16_t *ca, const uint
   HIP_TRY(hipMemcpyAsync(s.s_clue_b, cb, D * CLUES * sizeof(uint16_t), hipMemcpyHostToDevice, st));
   OMR_TRY(launch_first_level(c, (int)D, s.s_clue_a, s.s_clue_b, st));
   HIP_TRY(hipMemcpyAsync(lwe_int, s.lwe_int, D * (NI + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  OMR_TRY(lease.release());
+  HIP_TRY(hipStreamSynchronize(st));
+  return OMR_OK;
+}
+
+// launch_first_level after its rotations, on caller-supplied extracted LWEs: ext goes where br1 writes
+// it (scr.ext), then sum7 and launch_ks exactly as there.
+extern "C" omr_status omr_sum_key_switch(omr_ctx *c, const uint32_t *ext, size_t n, uint32_t *lwe_int) {
+  if (!c || !ext || !lwe_int || n == 0)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sum_key_switch: bad argument (n <= batch)");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (n > c->batch) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sum_key_switch: bad argument (n <= batch)");
+  const size_t words = n * CLUES * (N1 + 1);
+  for (size_t i = 0; i < words; ++i)
+    if (ext[i] >= (uint32_t)Q1)
+      return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sum_key_switch: ext holds a word >= q1");
+  HIP_TRY(hipSetDevice(c->device));
+  OMR_TRY(take_handoff_error(c));  // an earlier detect call's, never this call's (as detect_device does)
+  OMR_TRY(ensure_batch(c, n));
+  const omr_ctx::Scratch &s = c->scr;
+  hipStream_t st = c->stream;
+  ScratchLease lease;
+  OMR_TRY(lease.acquire(c, st));
+  HIP_TRY(hipMemcpyAsync(s.ext, ext, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  OMR_TRY(launch_sum_ks(c, (int)n, st));
+  HIP_TRY(hipMemcpyAsync(lwe_int, s.lwe_int, n * (NI + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   OMR_TRY(lease.release());
   HIP_TRY(hipStreamSynchronize(st));
   return OMR_OK;

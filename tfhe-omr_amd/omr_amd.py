@@ -182,6 +182,7 @@ EXPORTS = {
     "omr_digest_get_info": (C.c_int, [C.c_void_p, C.POINTER(_DigestInfo)]),
     "omr_digest_destroy": (None, [C.c_void_p]),
     "omr_first_level": (C.c_int, [C.c_void_p, _u16p, _u16p, C.c_size_t, _u32p]),
+    "omr_sum_key_switch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "omr_blind_rotate_level1": (C.c_int, [C.c_void_p, _u16p, _u16p, C.c_size_t, _u64p]),
     "omr_fft1_mul": (C.c_int, [C.c_void_p, _u32p, _u32p, C.c_size_t, _u64p]),
     "omr_decrypt_decode": (C.c_int, [C.c_void_p, _u64p, C.c_size_t, _u32p]),
@@ -1241,6 +1242,15 @@ class Detector:
         out = np.empty((clue_a.shape[0], NI + 1), np.uint32)
         _check(lib().omr_first_level(self._h, clue_a.reshape(-1), clue_b.reshape(-1), clue_a.shape[0],
                                      out.reshape(-1)), "omr_first_level")
+        return out
+
+    def sum_key_switch(self, ext) -> np.ndarray:
+        """The first level after its rotations on supplied extracted LWEs (u32 [n][7][1025], canonical): sum
+        of the seven, key switch, modulus switch, body offset; u32 [n][671] (omr_sum_key_switch)."""
+        ext = np.ascontiguousarray(ext, dtype=np.uint32).reshape(-1, CLUE_COUNT, N1 + 1)
+        out = np.empty((ext.shape[0], NI + 1), np.uint32)
+        _check(lib().omr_sum_key_switch(self._h, ext.ctypes.data, ext.shape[0], out.ctypes.data),
+               "omr_sum_key_switch")
         return out
 
     def blind_rotate_level1(self, lwe_a, lwe_b=None, acc0=None) -> np.ndarray:
