@@ -735,6 +735,78 @@ omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *sk, const ui
                                          uint16_t *payloads);
 
 /* ---------------------------------------------------------------------------------------
+ * Solve mod 257 — solve_matrix_mod_257 (matrix.rs:164-247), the elimination behind
+ * Retriever::decode_digest, as an operation of its own: on the CPU, and on an auditor's device.
+ *
+ * Definition. Every input word is reduced mod 257 first. The system is [matrix | rhs] with rows >= cols.
+ * For column i = 0 .. cols - 1:
+ *   - the pivot is the FIRST row j >= i whose current entry (j, i) is non-zero;
+ *   - rows i and j are swapped, in the matrix and in the rhs;
+ *   - row i is scaled by the inverse of its pivot;
+ *   - every row below i is reduced by its entry in column i times row i.
+ * After the last column back substitution clears the entries above the diagonal, and the solution is rows
+ * 0 .. cols - 1 of the rhs. If a column has no pivot the call reports OMR_ERR_NOT_INVERTIBLE ("Matrix is
+ * not invertible") and the column, and writes no solution.
+ *
+ * The arithmetic is exact and the pivot rule is fixed, so the result is a function of the inputs alone,
+ * also for an inconsistent system (rows > cols, e.g. a garbage digest), where the pivot rule decides which
+ * equations are solved. Any schedule that makes the same pivot choices gives the same bits;
+ * the device solver is a blocked one.
+ * ------------------------------------------------------------------------------------- */
+#define OMR_SOLVE_MAX_ROWS 8192
+/* matrix u16 [rows][cols], rhs u16 [rows][width], solution u16 [cols][width]; every input word is reduced
+ * mod 257 first. cols >= 1, rows >= cols, rows <= OMR_SOLVE_MAX_ROWS, width >= 1, else
+ * OMR_ERR_INVALID_ARGUMENT. OMR_ERR_NOT_INVERTIBLE sets *singular_col (it may be NULL) and leaves solution
+ * untouched. nthreads parallelises the row updates (<= 0: the host's cores, at most 16). */
+omr_status omr_solve_mod257_cpu(const uint16_t *matrix, const uint16_t *rhs, size_t rows, size_t cols,
+                                size_t width, uint16_t *solution, size_t *singular_col, int nthreads);
+/* Tile sizes of this build, so tests can place their shapes on the edges: the columns factorised per panel
+ * step, and the rows and columns of one tile of the trailing update. Any pointer may be NULL. */
+omr_status omr_solve_geometry(unsigned *panel_cols, unsigned *tile_rows, unsigned *tile_width);
+/* Device buffers of the auditor's device, 16-byte aligned. Inputs are not modified. d_status u32:
+ * 0 = solved, 1 + i = no pivot in column i (d_solution then not written). Enqueued on hip_stream
+ * (NULL = null stream), returns once enqueued. Works in scratch owned by the auditor (grown on
+ * demand: rows * (cols + width) words, each row padded to a multiple of 8 words); a call on another
+ * stream waits by event for the previous call's kernels, as detect does for the context's scratch. */
+omr_status omr_solve_mod257_device(omr_auditor *aud, const uint16_t *d_matrix, const uint16_t *d_rhs,
+                                   size_t rows, size_t cols, size_t width, uint16_t *d_solution,
+                                   uint32_t *d_status, void *hip_stream);
+/* Diagnostics for tools/retrieve_bench.py, not part of the stable interface (it may change or go with the
+ * solver's schedule; an auditor that never enables it records nothing): with enable != 0 every later
+ * omr_solve_mod257_device on the auditor records events around its steps; the call synchronises the auditor's last solve and writes the
+ * device time of that solve per step, milliseconds: step_ms[0] panel, [1] row swaps and pivot block,
+ * [2] trailing update, [3] back substitution (zeros if none was profiled). step_ms may be NULL. */
+omr_status omr_solve_profile(omr_auditor *aud, int enable, float step_ms[4]);
+
+/* Retrieval on the auditor: the CPU entry points above with the decode (audit_kernel), the system's
+ * right-hand side, the indexed matrix and the solve on the device. Ciphertexts come from host memory, full
+ * (bits = 0, u64 [n_ct][2][2048]) or compact (bits in [16, 32], n_ct x 512 bits bytes, expanded on the
+ * device), staged as omr_audit stages them; the decoded values stay on the device. Each call returns the
+ * same bits and the same status codes as its CPU twin (for bits != 0: the CPU call over
+ * omr_compact_expand_cpu's output), and OMR_ERR_INVALID_ARGUMENT ("more than OMR_SOLVE_MAX_ROWS
+ * combinations") for a system of more than OMR_SOLVE_MAX_ROWS rows. They return when done. */
+omr_status omr_auditor_retrieve_indices(omr_auditor *aud, const void *idx_cts, uint32_t n_ct, int bits,
+                                        size_t all_payloads_count, size_t pertinent_count, size_t *indices,
+                                        size_t cap, size_t *found);
+omr_status omr_auditor_retrieve_payloads(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
+                                         size_t all_payloads_count, uint32_t combination_count,
+                                         const uint16_t *weights, const size_t *indices, size_t n_indices,
+                                         uint16_t *payloads);
+omr_status omr_auditor_retrieve_payloads_indexed(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
+                                                 size_t all_payloads_count, uint32_t combination_count,
+                                                 const uint8_t weight_seed[32], const size_t *indices,
+                                                 size_t n_indices, uint16_t *payloads);
+/* decode_digest in one call, indexed weights: indices, then payloads of the indices found. The system
+ * has the board's rp.combination_count rows. cap < found is OMR_ERR_INVALID_ARGUMENT with *found set.
+ * summary (may be NULL) is added into with the audit of every ciphertext the call decoded (all of
+ * idx_cts and pay_cts). payloads u16 [found][612]. */
+omr_status omr_auditor_decode_digest_indexed(omr_auditor *aud, const void *idx_cts, uint32_t n_idx_ct,
+                                             const void *pay_cts, uint32_t n_pay_ct, int bits,
+                                             size_t all_payloads_count, size_t pertinent_count,
+                                             const uint8_t weight_seed[32], size_t *indices, size_t cap,
+                                             size_t *found, uint16_t *payloads, omr_audit_summary *summary);
+
+/* ---------------------------------------------------------------------------------------
  * Key audit (none in the reference): check a detection key against its secret before it is uploaded and
  * after any reload, and count non-canonical words at intake without a secret. A detector runs to
  * completion on a damaged key and returns well-formed ciphertexts that decrypt to "not pertinent"; this

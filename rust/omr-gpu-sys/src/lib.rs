@@ -373,6 +373,32 @@ pub mod ffi {
         pub fn omr_key_validate_seeded_device(key: *const OmrSeededKeyView, device: c_int,
                                               noncanonical: *mut u64) -> OmrStatus;
 
+        // solve mod 257 and retrieval on the auditor
+        pub fn omr_solve_mod257_cpu(matrix: *const u16, rhs: *const u16, rows: usize, cols: usize, width: usize,
+                                    solution: *mut u16, singular_col: *mut usize, nthreads: c_int) -> OmrStatus;
+        pub fn omr_solve_geometry(panel_cols: *mut c_uint, tile_rows: *mut c_uint, tile_width: *mut c_uint) -> OmrStatus;
+        pub fn omr_solve_mod257_device(aud: *mut OmrAuditor, d_matrix: *const u16, d_rhs: *const u16, rows: usize,
+                                       cols: usize, width: usize, d_solution: *mut u16, d_status: *mut u32,
+                                       hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_solve_profile(aud: *mut OmrAuditor, enable: c_int, step_ms: *mut f32) -> OmrStatus;
+        pub fn omr_auditor_retrieve_indices(aud: *mut OmrAuditor, idx_cts: *const c_void, n_ct: u32, bits: c_int,
+                                            all_payloads_count: usize, pertinent_count: usize, indices: *mut usize,
+                                            cap: usize, found: *mut usize) -> OmrStatus;
+        pub fn omr_auditor_retrieve_payloads(aud: *mut OmrAuditor, pay_cts: *const c_void, n_ct: u32, bits: c_int,
+                                             all_payloads_count: usize, combination_count: u32,
+                                             weights: *const u16, indices: *const usize, n_indices: usize,
+                                             payloads: *mut u16) -> OmrStatus;
+        pub fn omr_auditor_retrieve_payloads_indexed(aud: *mut OmrAuditor, pay_cts: *const c_void, n_ct: u32,
+                                                     bits: c_int, all_payloads_count: usize, combination_count: u32,
+                                                     weight_seed: *const u8, indices: *const usize, n_indices: usize,
+                                                     payloads: *mut u16) -> OmrStatus;
+        pub fn omr_auditor_decode_digest_indexed(aud: *mut OmrAuditor, idx_cts: *const c_void, n_idx_ct: u32,
+                                                 pay_cts: *const c_void, n_pay_ct: u32, bits: c_int,
+                                                 all_payloads_count: usize, pertinent_count: usize,
+                                                 weight_seed: *const u8, indices: *mut usize, cap: usize,
+                                                 found: *mut usize, payloads: *mut u16,
+                                                 summary: *mut OmrAuditSummary) -> OmrStatus;
+
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
                                lwe_int: *mut u32) -> OmrStatus;

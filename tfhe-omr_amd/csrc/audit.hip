@@ -7,6 +7,8 @@
 // omr_audit_compact run expand_kernel through compact.hpp, the latter in front of audit_kernel.
 // The key audit (include/omr_gpu.h, "Key audit"; key_audit_kernels.hpp) runs here too: the auditor keeps a
 // host copy of the pack's small secrets and, from its first key-audit call on, their device forms.
+// struct omr_auditor itself is in auditor.hpp, shared with retrieve_device.hip (the mod-257 solver and
+// retrieval), which decodes through audit_decode_to_device below.
 #include <algorithm>
 #include <memory>
 #include <mutex>
@@ -14,46 +16,13 @@
 #include <vector>
 
 #include "audit_kernels.hpp"
+#include "auditor.hpp"
 #include "compact.hpp"
 #include "hip_util.hpp"
 #include "host_tables.hpp"
 #include "key_audit_kernels.hpp"
 
 using namespace omr;
-
-struct omr_auditor {
-  int device = 0;
-  int num_cu = 0;
-  unsigned grid = 0;    // workgroups; 0: two per compute unit (audit_kernel), six (expand_kernel)
-  size_t staging = 0;   // ciphertexts per piece of omr_audit; 0: AUDIT_DEFAULT_STAGING
-  double ninv = 0.0;    // N2^-1 mod q2, centred
-  DevBuf<double> s2_ntt, itw, tw;  // tw: the forward twiddles, for expand_kernel only
-  // omr_audit's own stream and buffers (grown on demand, reused by later calls)
-  hipStream_t st = nullptr;
-  DevBuf<uint64_t> stage;
-  DevBuf<uint32_t> packed;  // omr_audit_compact's piece of compact ciphertexts, expanded into `stage`
-  DevBuf<omr_ct_audit> records;
-  DevBuf<uint16_t> decoded;
-  DevBuf<omr_audit_summary> summary;
-  // Key audit: the pack's secrets (host copies taken at creation) and, built by ensure_key_material on the
-  // first key-audit call, the level-1 tables, NTT(s1), the coefficient forms and the sigma_g(s2) table.
-  struct KeyMaterial {
-    std::vector<uint8_t> h_s0, h_sint;
-    std::vector<int8_t> h_s1, h_s2;
-    std::vector<uint64_t> h_s1_ntt;
-    bool ready = false;
-    double ninv1 = 0.0;
-    DevBuf<double> tw1, itw1, s1_ntt;
-    DevBuf<int8_t> s1, s2, sigma;
-    DevBuf<uint8_t> s0, sint;
-    DevBuf<omr_key_audit_summary> summary;
-  } key;
-  std::mutex mu;
-
-  ~omr_auditor() {
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
 
 namespace {
 
@@ -111,6 +80,7 @@ extern "C" void omr_auditor_destroy(omr_auditor *aud) {
   if (!aud) return;
   (void)hipSetDevice(aud->device);
   (void)hipStreamSynchronize(aud->st);
+  if (aud->solve.used) (void)hipEventSynchronize(aud->solve.free);
   delete aud;
 }
 
@@ -143,18 +113,13 @@ extern "C" omr_status omr_audit_device(omr_auditor *aud, const uint64_t *d_cts, 
 
 namespace {
 
-// The host entry points: n ciphertexts from host memory in pieces, full (bits = 0, src u64 [n][2][N2]) or
-// compact (src n x 512 bits bytes, expanded on the device in front of audit_kernel).
-omr_status audit_staged(omr_auditor *aud, const void *src, size_t n, int bits, omr_ct_audit *records,
-                        uint16_t *decoded, omr_audit_summary *summary, const char *who) {
-  const std::string name(who);
-  if (!aud) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": NULL auditor");
-  if (bits && !compact_bits_ok(bits)) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": bits must be in [16, 32]");
-  if (!records && !decoded && !summary) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": no output requested");
-  if (n == 0) return OMR_OK;
-  if (!src) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": NULL ciphertexts");
-  std::lock_guard<std::mutex> lk(aud->mu);
-  HIP_TRY(hipSetDevice(aud->device));
+// The staging loop of every host entry point: n > 0 ciphertexts from host memory in pieces on aud->st, full
+// (bits = 0, src u64 [n][2][N2]) or compact (src n x 512 bits bytes, expanded on the device in front of
+// audit_kernel). The decoded values go to the host (`decoded`, through the auditor's piece buffer) or stay on
+// the device (`d_decoded` u16 [n][2048], written in place); records and summary go to the host. Any output may
+// be NULL. Returns after the stream has finished. The caller holds aud->mu and has selected the device.
+omr_status audit_pieces(omr_auditor *aud, const void *src, size_t n, int bits, omr_ct_audit *records, uint16_t *decoded,
+                        uint16_t *d_decoded, omr_audit_summary *summary, const std::string &name) {
   const size_t B = std::min(n, aud->staging ? aud->staging : AUDIT_DEFAULT_STAGING);
   const size_t src_bytes = bits ? compact_ct_bytes(bits) : 2 * N2 * sizeof(uint64_t);  // per ciphertext
   hipStream_t st = aud->st;
@@ -171,12 +136,13 @@ omr_status audit_staged(omr_auditor *aud, const void *src, size_t n, int bits, o
   omr_status s = OMR_OK;
   for (size_t o = 0; o < n && s == OMR_OK; o += B) {
     const size_t k = std::min(B, n - o);
+    uint16_t *d_dec = d_decoded ? d_decoded + o * N2 : (decoded ? aud->decoded.get() : nullptr);
     hipError_t e = hipMemcpyAsync(d_src, (const uint8_t *)src + o * src_bytes, k * src_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && bits)
       s = launch_expand(aud->packed, k, bits, aud->tw, compact_grid(aud->grid, aud->num_cu, k), aud->stage, st);
     if (e == hipSuccess && s == OMR_OK)
-      s = launch_audit(aud, aud->stage, k, records ? aud->records.get() : nullptr,
-                       decoded ? aud->decoded.get() : nullptr, summary ? aud->summary.get() : nullptr, st);
+      s = launch_audit(aud, aud->stage, k, records ? aud->records.get() : nullptr, d_dec,
+                       summary ? aud->summary.get() : nullptr, st);
     if (e == hipSuccess && s == OMR_OK && records)
       e = hipMemcpyAsync(records + o, aud->records, k * sizeof(omr_ct_audit), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && s == OMR_OK && decoded)
@@ -195,7 +161,29 @@ omr_status audit_staged(omr_auditor *aud, const void *src, size_t n, int bits, o
   return s;
 }
 
+// omr_audit and omr_audit_compact: the argument checks, then the pieces with every result on the host.
+omr_status audit_staged(omr_auditor *aud, const void *src, size_t n, int bits, omr_ct_audit *records,
+                        uint16_t *decoded, omr_audit_summary *summary, const char *who) {
+  const std::string name(who);
+  if (!aud) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": NULL auditor");
+  if (bits && !compact_bits_ok(bits)) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": bits must be in [16, 32]");
+  if (!records && !decoded && !summary) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": no output requested");
+  if (n == 0) return OMR_OK;
+  if (!src) return set_error(OMR_ERR_INVALID_ARGUMENT, name + ": NULL ciphertexts");
+  std::lock_guard<std::mutex> lk(aud->mu);
+  HIP_TRY(hipSetDevice(aud->device));
+  return audit_pieces(aud, src, n, bits, records, decoded, nullptr, summary, name);
+}
+
 }  // namespace
+
+// The decode of retrieval on the auditor (auditor.hpp): the same pieces, the decoded values kept in the
+// caller's device buffer.
+omr_status omr::audit_decode_to_device(omr_auditor *aud, const void *src, size_t n, int bits, uint16_t *d_decoded,
+                                       omr_audit_summary *summary, const char *who) {
+  if (n == 0) return OMR_OK;
+  return audit_pieces(aud, src, n, bits, nullptr, nullptr, d_decoded, summary, who);
+}
 
 extern "C" omr_status omr_audit(omr_auditor *aud, const uint64_t *cts, size_t n, omr_ct_audit *records,
                                 uint16_t *decoded, omr_audit_summary *summary) {

@@ -3,7 +3,9 @@
 // solve_matrix_mod_257 (matrix.rs:164-247), and the bitmap digest's decoding (include/omr_gpu.h, "Bitmap
 // digest": none in the reference). Used by clients of the detector, by bench.py's
 // end-to-end check and by the multi-GPU driver; needs only the secret key pack.
+#include <algorithm>
 #include <mutex>
+#include <new>
 #include <set>
 #include <string>
 #include <vector>
@@ -126,6 +128,62 @@ extern "C" omr_status omr_retrieve_indices(const omr_secret_key_pack *sk, const 
 
 namespace {
 
+// Solve mod 257 (include/omr_gpu.h, "Solve mod 257"; solve_matrix_mod_257, matrix.rs:164-247) on the
+// augmented system [matrix | rhs], any number of rows: forward elimination with the first non-zero pivot,
+// then back substitution. nthreads > 1 splits the rows below the pivot once there is enough of them.
+omr_status solve_mod257(const uint16_t *matrix, const uint16_t *rhs, size_t rows, size_t cols, size_t width,
+                        uint16_t *solution, size_t *singular_col, int nthreads) {
+  const size_t ld = cols + width;
+  std::vector<uint16_t> w(rows * ld);  // values < 257
+  for (size_t j = 0; j < rows; ++j) {
+    for (size_t k = 0; k < cols; ++k) w[j * ld + k] = matrix[j * cols + k] % P;
+    for (size_t b = 0; b < width; ++b) w[j * ld + cols + b] = rhs[j * width + b] % P;
+  }
+  uint16_t inv[P] = {0};  // v^(p-2) mod p
+  for (uint32_t v = 1; v < (uint32_t)P; ++v) {
+    uint32_t r = 1, b = v;
+    for (uint32_t e = P - 2; e; e >>= 1, b = b * b % P)
+      if (e & 1) r = r * b % P;
+    inv[v] = (uint16_t)r;
+  }
+  // row j -= c * row i over the columns [k0, ld)
+  auto reduce = [&](size_t j, size_t i, size_t col, size_t k0) {
+    const uint32_t c = w[j * ld + col];
+    if (!c) return;
+    uint16_t *rj = &w[j * ld];
+    const uint16_t *ri = &w[i * ld];
+    for (size_t k = k0; k < ld; ++k) rj[k] = (uint16_t)((rj[k] + (uint32_t)P * P - c * ri[k]) % P);
+  };
+  for (size_t i = 0; i < cols; ++i) {
+    size_t piv = rows;
+    for (size_t j = i; j < rows; ++j)
+      if (w[j * ld + i] != 0) {
+        piv = j;
+        break;
+      }
+    if (piv == rows) {
+      if (singular_col) *singular_col = i;
+      return set_error(OMR_ERR_NOT_INVERTIBLE, "Matrix is not invertible");
+    }
+    if (piv != i) std::swap_ranges(&w[i * ld], &w[i * ld] + ld, &w[piv * ld]);
+    if (w[i * ld + i] != 1) {
+      const uint32_t iv = inv[w[i * ld + i]];
+      for (size_t k = i; k < ld; ++k) w[i * ld + k] = (uint16_t)(w[i * ld + k] * iv % P);
+    }
+    const size_t below = rows - i - 1;
+    if (nthreads == 1 || below * (ld - i) < ((size_t)1 << 18)) {
+      for (size_t j = i + 1; j < rows; ++j) reduce(j, i, i, i);
+    } else {
+      parallel_for(below, nthreads, [&](size_t r) { reduce(i + 1 + r, i, i, i); });
+    }
+  }
+  for (size_t i = cols; i-- > 1;)
+    for (size_t j = 0; j < i; ++j) reduce(j, i, i, cols);  // the matrix part above the diagonal is not read again
+  for (size_t k = 0; k < cols; ++k)
+    for (size_t b = 0; b < width; ++b) solution[k * width + b] = w[k * ld + cols + b];
+  return OMR_OK;
+}
+
 // The body of omr_retrieve_payloads and omr_retrieve_payloads_indexed after their NULL checks: they
 // differ in where the system's matrix comes from. fill(rows, m) writes m[j][k], the weight of combination
 // j for the k-th index, and returns a status.
@@ -147,53 +205,17 @@ omr_status retrieve_payloads_body(const omr_secret_key_pack *sk, const uint64_t 
     if (indices[i] >= all_payloads_count)
       return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": index out of range");
   // decode_combined_payloads: combination j lives in ciphertext j / per, slots (j % per) * 612..
-  std::vector<std::vector<uint32_t>> rhs(rows, std::vector<uint32_t>(PAYLOAD_LEN));
+  std::vector<uint16_t> rhs(rows * PAYLOAD_LEN);
   std::vector<uint32_t> dec((size_t)n_ct * N2);
   parallel_for(n_ct, 0, [&](size_t c) { decrypt_decode_one(sk, pay_cts + c * 2 * N2, P, &dec[c * N2]); });
   for (size_t j = 0; j < rows; ++j)
-    for (int b = 0; b < PAYLOAD_LEN; ++b) rhs[j][b] = dec[(j / per) * N2 + (j % per) * PAYLOAD_LEN + b];
+    for (int b = 0; b < PAYLOAD_LEN; ++b)
+      rhs[j * PAYLOAD_LEN + b] = (uint16_t)dec[(j / per) * N2 + (j % per) * PAYLOAD_LEN + b];
   // matrix[j][k] = weight of combination j for the k-th retrieved index (retriever.rs:220-238)
-  std::vector<std::vector<uint32_t>> m(rows, std::vector<uint32_t>(cols));
-  if ((st = fill(rows, m)) != OMR_OK) return st;
-  auto inv = [](uint32_t v) {  // v^(p-2) mod p
-    uint32_t r = 1, b = v % P;
-    for (uint32_t e = P - 2; e; e >>= 1, b = b * b % P)
-      if (e & 1) r = r * b % P;
-    return r;
-  };
-  // forward elimination with the first non-zero pivot, then back substitution (matrix.rs)
-  for (size_t i = 0; i < cols; ++i) {
-    size_t piv = rows;
-    for (size_t j = i; j < rows; ++j)
-      if (m[j][i] != 0) {
-        piv = j;
-        break;
-      }
-    if (piv == rows) return set_error(OMR_ERR_NOT_INVERTIBLE, "Matrix is not invertible");
-    std::swap(m[i], m[piv]);
-    std::swap(rhs[i], rhs[piv]);
-    if (m[i][i] != 1) {
-      const uint32_t iv = inv(m[i][i]);
-      for (size_t k = i; k < cols; ++k) m[i][k] = m[i][k] * iv % P;
-      for (auto &x : rhs[i]) x = x * iv % P;
-    }
-    for (size_t j = i + 1; j < rows; ++j) {
-      const uint32_t c = m[j][i];
-      if (!c) continue;
-      for (size_t k = i; k < cols; ++k) m[j][k] = (m[j][k] + P * P - c * m[i][k]) % P;
-      for (int b = 0; b < PAYLOAD_LEN; ++b) rhs[j][b] = (rhs[j][b] + P * P - c * rhs[i][b]) % P;
-    }
-  }
-  for (size_t i = cols; i-- > 1;)
-    for (size_t j = 0; j < i; ++j) {
-      const uint32_t c = m[j][i];
-      if (!c) continue;
-      for (int b = 0; b < PAYLOAD_LEN; ++b) rhs[j][b] = (rhs[j][b] + P * P - c * rhs[i][b]) % P;
-      m[j][i] = 0;
-    }
-  for (size_t k = 0; k < cols; ++k)
-    for (int b = 0; b < PAYLOAD_LEN; ++b) payloads[k * PAYLOAD_LEN + b] = (uint16_t)rhs[k][b];
-  return OMR_OK;
+  std::vector<uint16_t> m(rows * cols);
+  if ((st = fill(rows, m.data())) != OMR_OK) return st;
+  // forward elimination with the first non-zero pivot, then back substitution (matrix.rs), on this thread
+  return solve_mod257(m.data(), rhs.data(), rows, cols, PAYLOAD_LEN, payloads, nullptr, 1);
 }
 
 }  // namespace
@@ -206,10 +228,10 @@ extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const
   if (!sk || !pay_cts || !weights || (n_indices && (!indices || !payloads)))
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: NULL argument");
   return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
-                                "omr_retrieve_payloads", [&](size_t rows, std::vector<std::vector<uint32_t>> &m) {
+                                "omr_retrieve_payloads", [&](size_t rows, uint16_t *m) {
                                   for (size_t j = 0; j < rows; ++j)
                                     for (size_t k = 0; k < n_indices; ++k)
-                                      m[j][k] = weights[j * all_payloads_count + indices[k]] % P;
+                                      m[j * n_indices + k] = weights[j * all_payloads_count + indices[k]];
                                   return OMR_OK;
                                 });
 }
@@ -222,16 +244,24 @@ extern "C" omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *s
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_indexed: NULL argument");
   return retrieve_payloads_body(
       sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
-      "omr_retrieve_payloads_indexed", [&](size_t rows, std::vector<std::vector<uint32_t>> &m) {
+      "omr_retrieve_payloads_indexed", [&](size_t rows, uint16_t *m) {
         // every row is a real combination of the board: rows = combination_count (or its default)
-        std::vector<uint16_t> w(rows * n_indices);
-        const omr_status s = omr_indexed_weights_at(weight_seed, (uint32_t)rows, 0, (uint32_t)rows, indices,
-                                                    n_indices, w.data(), 0);
-        if (s != OMR_OK) return s;
-        for (size_t j = 0; j < rows; ++j)
-          for (size_t k = 0; k < n_indices; ++k) m[j][k] = w[j * n_indices + k] % P;
-        return OMR_OK;
+        return omr_indexed_weights_at(weight_seed, (uint32_t)rows, 0, (uint32_t)rows, indices, n_indices, m, 0);
       });
+}
+
+extern "C" omr_status omr_solve_mod257_cpu(const uint16_t *matrix, const uint16_t *rhs, size_t rows, size_t cols,
+                                           size_t width, uint16_t *solution, size_t *singular_col, int nthreads) {
+  if (!matrix || !rhs || !solution) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_solve_mod257_cpu: NULL argument");
+  if (cols < 1 || rows < cols || width < 1)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_solve_mod257_cpu: needs cols >= 1, rows >= cols, width >= 1");
+  if (rows > OMR_SOLVE_MAX_ROWS)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_solve_mod257_cpu: more than OMR_SOLVE_MAX_ROWS (8192) rows");
+  try {
+    return solve_mod257(matrix, rhs, rows, cols, width, solution, singular_col, nthreads);
+  } catch (const std::bad_alloc &) {
+    return set_error(OMR_ERR_OUT_OF_MEMORY, "omr_solve_mod257_cpu: host allocation failed");
+  }
 }
 
 extern "C" omr_status omr_bitmap_ct_count(size_t all, uint32_t *n_ct) {

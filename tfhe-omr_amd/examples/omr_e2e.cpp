@@ -5,7 +5,7 @@
 // indices and their payloads come back.
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
-//           [--compact BITS] [--audit-key] [--indexed-weights] [--host-only]
+//           [--compact BITS] [--audit-key] [--indexed-weights] [--device-retrieve] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -28,6 +28,10 @@
 // --audit-key audits the detection key it generated against the recipient's secret on the GPU before the
 // detector is created (omr_audit_key, or omr_audit_key_seeded with --seeded; include/omr_gpu.h, "Key audit"):
 // a row whose noise lies outside the generators' support, in any component, fails the run.
+// --device-retrieve makes the recipient retrieve on an auditor (include/omr_gpu.h, "Solve mod 257":
+// omr_auditor_retrieve_indices, omr_auditor_retrieve_payloads[_indexed]): decode, right-hand side and the
+// mod-257 solve run on the device. With --compact the auditor takes the packed digest as it arrived and
+// expands it on the device; with --indexed-weights it builds the matrix there too.
 // --indexed-weights uses indexed payload weights on both sides (include/omr_gpu.h, "Indexed payload weights"):
 // the detector encodes with omr_encode_payloads_indexed (or a session from omr_digest_begin_indexed) and the
 // recipient solves with omr_retrieve_payloads_indexed; nobody draws the board-wide weight table. With
@@ -73,7 +77,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false;
+  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false, device_retrieve = false;
   int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -87,10 +91,11 @@ int main(int argc, char **argv) {
     else if (a == "--compact" && i + 1 < argc) compact_bits = std::atoi(argv[++i]);
     else if (a == "--audit-key") audit_key = true;
     else if (a == "--indexed-weights") indexed = true;
+    else if (a == "--device-retrieve") device_retrieve = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--host-only]\n",
+                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--device-retrieve] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -396,23 +401,37 @@ int main(int argc, char **argv) {
   t = clk::now();
   std::vector<size_t> found(pert_count + 64);
   size_t nfound = 0;
+  // --device-retrieve: the recipient's auditor takes the digest in the form it arrived in
+  omr_auditor *ra = nullptr;
+  if (device_retrieve) CHECK(omr_auditor_create(pa, device, &ra));
+  const void *dev_idx = compact_bits ? (const void *)idx_pk.data() : (const void *)idx_ct.data();
+  const void *dev_pay = compact_bits ? (const void *)pay_pk.data() : (const void *)pay_ct.data();
   if (bitmap) {
     // no count needed: the bitmap says how many there are, and whether the board's layout covers them
     CHECK(omr_retrieve_bitmap(pa, bmp_ct.data(), n_bmp, D, found.data(), found.size(), &nfound));
     std::printf("bitmap digest: %u ciphertexts, %zu pertinent indices (the board's %u combinations %s)\n", n_bmp,
                 nfound, rp.combination_count, nfound <= rp.combination_count ? "cover them" : "do NOT cover them");
+  } else if (device_retrieve) {
+    CHECK(omr_auditor_retrieve_indices(ra, dev_idx, n_idx, compact_bits, D, pert_count, found.data(), found.size(), &nfound));
   } else {
     CHECK(omr_retrieve_indices(pa, idx_ct.data(), n_idx, D, pert_count, found.data(), found.size(), &nfound));
   }
   found.resize(std::min(nfound, found.size()));
   std::vector<uint16_t> solved(found.size() * PAYLOAD);
-  if (indexed)
+  if (device_retrieve && indexed)
+    CHECK(omr_auditor_retrieve_payloads_indexed(ra, dev_pay, n_pay, compact_bits, D, rp.combination_count, wseed,
+                                                found.data(), found.size(), solved.data()));
+  else if (device_retrieve)
+    CHECK(omr_auditor_retrieve_payloads(ra, dev_pay, n_pay, compact_bits, D, rp.combination_count, weights.data(),
+                                        found.data(), found.size(), solved.data()));
+  else if (indexed)
     CHECK(omr_retrieve_payloads_indexed(pa, pay_ct.data(), n_pay, D, rp.combination_count, wseed, found.data(),
                                         found.size(), solved.data()));
   else
     CHECK(omr_retrieve_payloads(pa, pay_ct.data(), n_pay, D, rp.combination_count, weights.data(), found.data(),
                                 found.size(), solved.data()));
-  std::printf("decode time: %.3f s\n", secs(t));
+  std::printf("decode time: %.3f s%s\n", secs(t), device_retrieve ? " (on the auditor's device)" : "");
+  omr_auditor_destroy(ra);
 
   int fails = (found == pert ? 0 : 1) + audit_fails + compact_fails;
   if (fails) std::printf("Fail: %zu indices recovered, %zu pertinent\n", found.size(), pert.size());

@@ -231,6 +231,21 @@ EXPORTS = {
     "omr_blind_rotate_level2_from": (C.c_int, [C.c_void_p, _u32p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "omr_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "omr_ntt": (C.c_int, [C.c_int, C.c_int, _u64p, C.c_size_t, C.c_int]),
+    "omr_solve_mod257_cpu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                       C.POINTER(C.c_size_t), C.c_int]),
+    "omr_solve_geometry": (C.c_int, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "omr_solve_mod257_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_solve_profile": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float * 4)]),
+    "omr_auditor_retrieve_indices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_size_t, C.c_size_t,
+                                               C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "omr_auditor_retrieve_payloads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_size_t, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "omr_auditor_retrieve_payloads_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_size_t,
+                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "omr_auditor_decode_digest_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
+                                                    C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -667,6 +682,45 @@ class Retriever:
         return indices, self.decode_combined_payloads_and_solve(pay_cts, weights, indices)
 
 
+# ---- solve mod 257 (include/omr_gpu.h, "Solve mod 257") ---------------------------------------
+SOLVE_MAX_ROWS = 8192
+NOT_INVERTIBLE = 4  # OMR_ERR_NOT_INVERTIBLE
+
+
+class SingularMatrix(OmrError):
+    """OMR_ERR_NOT_INVERTIBLE of a solve: `column` is the first column without a pivot."""
+
+    def __init__(self, column: int):
+        super().__init__(f"omr_solve_mod257 failed ({NOT_INVERTIBLE}): Matrix is not invertible (column {column})")
+        self.column = column
+
+
+def solve_geometry() -> dict:
+    """omr_solve_geometry: {'panel_cols', 'tile_rows', 'tile_width'} of the device solver of this build."""
+    p, r, w = C.c_uint(), C.c_uint(), C.c_uint()
+    _check(lib().omr_solve_geometry(C.byref(p), C.byref(r), C.byref(w)), "omr_solve_geometry")
+    return {"panel_cols": p.value, "tile_rows": r.value, "tile_width": w.value}
+
+
+def solve_mod257_cpu(matrix, rhs, nthreads: int = 1) -> np.ndarray:
+    """omr_solve_mod257_cpu: the solution u16 [cols][width] of [matrix | rhs] mod 257 (matrix u16 [rows][cols],
+    rhs u16 [rows][width], words reduced mod 257 first) by solve_matrix_mod_257's elimination; raises
+    SingularMatrix (with the column) when a column has no pivot."""
+    m = np.ascontiguousarray(matrix, dtype=np.uint16)
+    r = np.ascontiguousarray(rhs, dtype=np.uint16)
+    if m.ndim != 2 or r.ndim != 2 or m.shape[0] != r.shape[0]:
+        raise OmrError("solve_mod257_cpu: matrix [rows][cols] and rhs [rows][width] expected")
+    rows, cols = m.shape
+    out = np.zeros((cols, r.shape[1]), np.uint16)
+    col = C.c_size_t()
+    st = lib().omr_solve_mod257_cpu(m.ctypes.data, r.ctypes.data, rows, cols, r.shape[1], out.ctypes.data,
+                                    C.byref(col), nthreads)
+    if st == NOT_INVERTIBLE:
+        raise SingularMatrix(col.value)
+    _check(st, "omr_solve_mod257_cpu")
+    return out
+
+
 # ---- compact ciphertexts (include/omr_gpu.h, "Compact ciphertexts") ---------------------------
 COMPACT_MIN_BITS, COMPACT_MAX_BITS = 16, 32
 
@@ -931,6 +985,82 @@ class Auditor:
         _check(lib().omr_audit_key_rows_device(self._h, component, d_rows or None, first_row, rows, limit,
                                                d_row_max or None, d_summary or None, stream or None),
                "omr_audit_key_rows_device")
+
+    # ---- solve mod 257 and retrieval on the device (include/omr_gpu.h, "Solve mod 257") ----
+    def solve_mod257_device(self, d_matrix: int, d_rhs: int, rows: int, cols: int, width: int, d_solution: int,
+                            d_status: int, stream: int = 0) -> None:
+        """Device pointers (omr_solve_mod257_device): d_matrix u16 [rows][cols], d_rhs u16 [rows][width],
+        d_solution u16 [cols][width], d_status u32 (0 = solved, 1 + i = no pivot in column i, d_solution then
+        not written). Enqueued on `stream`; the caller synchronises."""
+        _check(lib().omr_solve_mod257_device(self._h, d_matrix or None, d_rhs or None, rows, cols, width,
+                                             d_solution or None, d_status or None, stream or None),
+               "omr_solve_mod257_device")
+
+    def solve_profile(self, enable: bool = True) -> list:
+        """omr_solve_profile: synchronises the last solve and returns its device milliseconds per step [panel,
+        swaps and pivot block, trailing update, back substitution] (zeros unless it was profiled); later solves
+        are profiled if `enable`."""
+        ms = (C.c_float * 4)()
+        _check(lib().omr_solve_profile(self._h, int(enable), C.byref(ms)), "omr_solve_profile")
+        return [float(v) for v in ms]
+
+    @staticmethod
+    def _cts(cts, bits: int) -> np.ndarray:
+        """Full (bits = 0: u64 [n][2][2048]) or compact (u8 [n][512 * bits]) ciphertexts, n in shape[0]."""
+        if bits:
+            return _packed(cts, bits)
+        return np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, N2)
+
+    def retrieve_indices(self, idx_cts, all_payloads_count: int, pertinent_count: int, bits: int = 0,
+                         cap: int = None) -> list:
+        """omr_auditor_retrieve_indices: Retriever.decode_pertinent_indices with the decode on the device; every
+        index found, increasing."""
+        c = self._cts(idx_cts, bits)
+        return _indices_call(lambda i, n, f: lib().omr_auditor_retrieve_indices(
+            self._h, c.ctypes.data, c.shape[0], bits, all_payloads_count, pertinent_count, i, n, f),
+            "omr_auditor_retrieve_indices", max(1, pertinent_count) * 4 + 64 if cap is None else cap)
+
+    def retrieve_payloads(self, pay_cts, all_payloads_count: int, combination_count: int, weights, indices,
+                          bits: int = 0) -> np.ndarray:
+        """omr_auditor_retrieve_payloads: u16 [len(indices)][612], the table path of
+        Retriever.decode_combined_payloads_and_solve with decode, right-hand side and solve on the device."""
+        c = self._cts(pay_cts, bits)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        w = np.ascontiguousarray(weights, dtype=np.uint16).reshape(-1)
+        out = np.zeros((len(idx), PAYLOAD_LENGTH), np.uint16)
+        _check(lib().omr_auditor_retrieve_payloads(self._h, c.ctypes.data, c.shape[0], bits, all_payloads_count,
+                                                   combination_count, w.ctypes.data, idx.ctypes.data, len(idx),
+                                                   out.ctypes.data), "omr_auditor_retrieve_payloads")
+        return out
+
+    def retrieve_payloads_indexed(self, pay_cts, all_payloads_count: int, combination_count: int, seed: bytes, indices,
+                                  bits: int = 0) -> np.ndarray:
+        """omr_auditor_retrieve_payloads_indexed: the same with the matrix built on the device from the indexed
+        weights of `seed`."""
+        c = self._cts(pay_cts, bits)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        out = np.zeros((len(idx), PAYLOAD_LENGTH), np.uint16)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_auditor_retrieve_payloads_indexed(self._h, c.ctypes.data, c.shape[0], bits, all_payloads_count,
+                                                           combination_count, ptr, idx.ctypes.data, len(idx),
+                                                           out.ctypes.data), "omr_auditor_retrieve_payloads_indexed")
+        return out
+
+    def decode_digest(self, idx_cts, pay_cts, seed: bytes, all_payloads_count: int, pertinent_count: int, bits: int = 0,
+                      cap: int = None):
+        """omr_auditor_decode_digest_indexed: Retriever.decode_digest(indexed=True) in one call on the device:
+        (sorted indices, payloads u16 [found][612], summary dict of every ciphertext decoded)."""
+        ci, cp = self._cts(idx_cts, bits), self._cts(pay_cts, bits)
+        cap = max(1, pertinent_count) * 4 + 64 if cap is None else cap
+        idx = np.zeros(max(1, cap), dtype=np.uintp)
+        out = np.zeros((max(1, cap), PAYLOAD_LENGTH), np.uint16)
+        found, t = C.c_size_t(), _AuditSummary()
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_auditor_decode_digest_indexed(self._h, ci.ctypes.data, ci.shape[0], cp.ctypes.data, cp.shape[0],
+                                                       bits, all_payloads_count, pertinent_count, ptr, idx.ctypes.data,
+                                                       cap, C.byref(found), out.ctypes.data, C.addressof(t)),
+               "omr_auditor_decode_digest_indexed")
+        return [int(v) for v in idx[:found.value]], out[:found.value].copy(), _summary_dict(t)
 
     @staticmethod
     def summary_from_bytes(buf) -> dict:
