@@ -341,6 +341,32 @@ omr_status omr_ctx_rounding_margin(omr_ctx *ctx, double observed[2], double apri
  * breaches[l] counts the launches of level l + 1 whose margin reached the threshold. Any pointer
  * may be NULL. Reading breaches synchronises the device. */
 omr_status omr_ctx_exactness(omr_ctx *ctx, int guarded[2], uint64_t breaches[2]);
+/* The launch record: which level-2 rotation and trace kernel the context's calls ran. Every entry point
+ * that reaches level 2 (detect, omr_second_level, omr_blind_rotate_level2[_from], omr_trace) chooses its
+ * kernels on the host -- by size, guard, a priori bounds, and whether the cooperative two-CU launch fits
+ * and the runtime accepts it, falling back silently otherwise. counts[k] is the cumulative number of
+ * launches of kind k since the context was created (the counters are never reset: compare two reads).
+ * Host integers only, incremented under the context's mutex where the choice is made: the record adds no
+ * kernel argument, device memory or synchronisation. */
+typedef enum {
+  /* the level-2 rotation of one launch: exactly one of these five */
+  OMR_LAUNCH_BR2F = 0,       /* throughput, FFT (br2f_kernel) */
+  OMR_LAUNCH_BR2F_GUARD = 1, /* throughput, guarded FFT (br2f_guard_kernel) */
+  OMR_LAUNCH_BR2L = 2,       /* latency, one workgroup per message, NTT (br2l_kernel) */
+  OMR_LAUNCH_BR2X = 3,       /* latency, two CUs per message, NTT (br2x_kernel), cooperative */
+  OMR_LAUNCH_BR2Y = 4,       /* latency, two CUs per message, FFT (br2y_kernel), cooperative */
+  OMR_LAUNCH_BR2Y_HELPERS = 5, /* of the BR2Y launches, those that carried the key-prefetch helper rows */
+  OMR_LAUNCH_BR2_FROM = 6,   /* of the five, those on the kernel's _from instantiation (a supplied acc0) */
+  OMR_LAUNCH_GUARD_FALLBACK = 7, /* guarded level-2 launches (rotation, or omr_trace's trace) followed by
+                                  * the conditional exact fallback kernels */
+  /* the trace of one launch: exactly one of these four */
+  OMR_LAUNCH_TRACE_FFT = 8,       /* throughput, FFT (trace_fft_kernel) */
+  OMR_LAUNCH_TRACE_FFT_GUARD = 9, /* throughput, guarded FFT (trace_fft_guard_kernel) */
+  OMR_LAUNCH_TRACE_X = 10,        /* latency, TRACE_X CUs per message (trace_x_kernel), cooperative */
+  OMR_LAUNCH_TRACE_KERNEL = 11,   /* one workgroup per message, NTT (trace_kernel) */
+  OMR_LAUNCH_COUNT = 12
+} omr_launch_kind;
+omr_status omr_ctx_launch_record(omr_ctx *ctx, uint64_t counts[OMR_LAUNCH_COUNT]);
 /* Level 1 on the exact modular NTT for every launch of the context (br1n_kernel: the reference's
  * own arithmetic, concrete-ntt in BlindRotationKey::blind_rotate, detector.rs:553-557), instead of the
  * FFT kernels; enable = 0 restores them. Outputs are bit-identical either way -- a cross-check of
@@ -914,7 +940,10 @@ omr_status omr_blind_rotate_level2(omr_ctx *ctx, const uint32_t *lwe_int, size_t
  * and an LWE with one nonzero a_i runs exactly one CMUX step on that step's key rows. acc0 == NULL
  * behaves exactly as the entry without _from. A word >= q is OMR_ERR_INVALID_ARGUMENT, checked on
  * the host before anything is enqueued. The same kernel selection, guard and fallback as the
- * matching entry, on those kernels' _from instantiations. */
+ * matching entry, on those kernels' _from instantiations: at level 2 that includes the latency path's
+ * two-CU kernels (br2y_from_kernel, or br2x_from_kernel on a guarded context or with OMR_BR2Y=0), with
+ * br2l's only where the entry without _from would run br2l_kernel (the cooperative launch does not fit
+ * or is refused). omr_ctx_launch_record tells which ran. */
 omr_status omr_blind_rotate_level1_from(omr_ctx *ctx, const uint16_t *lwe_a, const uint16_t *lwe_b,
                                         size_t n, const uint64_t *acc0, uint64_t *out);
 omr_status omr_blind_rotate_level2_from(omr_ctx *ctx, const uint32_t *lwe_int, size_t n,

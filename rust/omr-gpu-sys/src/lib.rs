@@ -158,6 +158,20 @@ pub mod ffi {
     pub const OMR_KEY_KSK: c_int = 1;
     pub const OMR_KEY_BSK2: c_int = 2;
     pub const OMR_KEY_TRACE: c_int = 3;
+    /// `omr_launch_kind`: the indices of `omr_ctx_launch_record`'s counters.
+    pub const OMR_LAUNCH_BR2F: usize = 0;
+    pub const OMR_LAUNCH_BR2F_GUARD: usize = 1;
+    pub const OMR_LAUNCH_BR2L: usize = 2;
+    pub const OMR_LAUNCH_BR2X: usize = 3;
+    pub const OMR_LAUNCH_BR2Y: usize = 4;
+    pub const OMR_LAUNCH_BR2Y_HELPERS: usize = 5;
+    pub const OMR_LAUNCH_BR2_FROM: usize = 6;
+    pub const OMR_LAUNCH_GUARD_FALLBACK: usize = 7;
+    pub const OMR_LAUNCH_TRACE_FFT: usize = 8;
+    pub const OMR_LAUNCH_TRACE_FFT_GUARD: usize = 9;
+    pub const OMR_LAUNCH_TRACE_X: usize = 10;
+    pub const OMR_LAUNCH_TRACE_KERNEL: usize = 11;
+    pub const OMR_LAUNCH_COUNT: usize = 12;
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
     pub struct OmrDetectTiming {
@@ -260,6 +274,7 @@ pub mod ffi {
         pub fn omr_ctx_rounding_margin(ctx: *mut OmrCtx, observed: *mut f64, apriori: *mut f64, kappa: *mut f64,
                                        reset: c_int) -> OmrStatus;
         pub fn omr_ctx_exactness(ctx: *mut OmrCtx, guarded: *mut c_int, breaches: *mut u64) -> OmrStatus;
+        pub fn omr_ctx_launch_record(ctx: *mut OmrCtx, counts: *mut u64) -> OmrStatus;
         pub fn omr_fft_twiddles_dd(level: c_int, out: *mut f64) -> OmrStatus;
         pub fn omr_ctx_key_spectrum(ctx: *mut OmrCtx, level: c_int, first: usize, count: usize,
                                     out: *mut f64) -> OmrStatus;
@@ -914,6 +929,14 @@ impl GpuDetector {
         let (mut g, mut b) = ([0 as c_int; 2], [0u64; 2]);
         check(unsafe { omr_ctx_exactness(self.ctx, g.as_mut_ptr(), b.as_mut_ptr()) })?;
         Ok(([g[0] != 0, g[1] != 0], b))
+    }
+
+    /// The launch record (`omr_ctx_launch_record`): cumulative launches per level-2 rotation / trace
+    /// kernel since creation, indexed by the `OMR_LAUNCH_*` constants. Host counters.
+    pub fn launch_record(&self) -> Result<[u64; OMR_LAUNCH_COUNT], OmrError> {
+        let mut counts = [0u64; OMR_LAUNCH_COUNT];
+        check(unsafe { omr_ctx_launch_record(self.ctx, counts.as_mut_ptr()) })?;
+        Ok(counts)
     }
 
     /// Chunks of at most `max_messages` messages run the latency kernels (0 = never).

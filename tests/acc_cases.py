@@ -10,7 +10,7 @@ omr_trace takes any RLWE. Two facts make every decomposition input reachable:
 
 Every function is deterministic, pure numpy plus the oracle, and returns (lwe, acc0) for one message
 (the trace functions: one RLWE). cases(level, dk) / trace_cases(dk) give the whole named set, about a
-dozen messages each. tests/test_acc_cases_host.py proves on the CPU that the set holds what it claims.
+dozen messages each (level 2: 19, with the cases for the two-CU latency kernels). tests/test_acc_cases_host.py proves on the CPU that the set holds what it claims.
 """
 import numpy as np
 
@@ -321,6 +321,48 @@ def random_case(L, dk, seed=77):
     return lwe_for(L, {i: L.N}), rng.integers(0, L.q, (2, L.N), dtype=np.uint64)
 
 
+# ---- the two-CU schedule (level 2) -----------------------------------------------------------------
+# Executed steps of steps_many: boundary targets at step 0, then two consecutive steps, a gap (the key rows
+# held for step 3 are not step 7's), and the last two steps (the last one has no next row to load). Six
+# hand-offs: each payload slot (the step count's parity) is reused twice, and the key prefetchers' lead of
+# two executed steps binds.
+STEPS_MANY = lambda L: {0: L.N, 1: 3, 2: L.N + 1, 7: 1, L.last_step - 1: 2 * L.N - 1, L.last_step: L.N}  # noqa: E731
+
+
+def word_split_digits(L):
+    """{"low_zero": (digits +, digits -), "high_zero": (digits +, digits -)}: the lower half of the digits
+    (the first digit word of the level-2 FFT kernels: digits 0..2) all zero while the upper half sits at its
+    extremes of one sign (the top digit the largest that fits, as in extreme_digits), and the reverse."""
+    half = L.d // 2
+    pos, neg = extreme_digits(L)
+    out = {"high_zero": ([L.B // 2 - 1] * half + [0] * (L.d - half), [-(L.B // 2)] * half + [0] * (L.d - half))}
+    low = []
+    for ext, step in ((pos, -1), (neg, 1)):
+        dg = [0] * half + list(ext[half:])
+        while not (abs(from_digits(L, dg)) <= L.h and decompose(L, from_digits(L, dg)) == dg):
+            dg[-1] += step
+        low.append(dg)
+    out["low_zero"] = (low[0], low[1])
+    return out
+
+
+def word_split_case(L, which, poly):
+    """One step (a = N) in which every coefficient of polynomial `poly` (0 mask, 1 body) decomposes to
+    word_split_digits(L)[which], the sign by a fixed coin per coefficient, and the other polynomial is zero:
+    one half of the digit polynomials is all-zero beside a half at its extremes, and the partner polynomial's
+    digits are all zero."""
+    dp, dn = word_split_digits(L)[which]
+    tp, tn = from_digits(L, dp), from_digits(L, dn)
+    coin = np.random.default_rng(40 + poly + 2 * (which == "low_zero")).integers(0, 2, L.N)
+    acc = acc_for_target([tp if c else tn for c in coin], L.q)
+    zero = np.zeros(L.N, dtype=np.uint64)
+    return lwe_for(L, {0: L.N}), np.stack([acc, zero] if poly == 0 else [zero, acc])
+
+
+WORD_SPLIT = [(w, p) for w in ("low_zero", "high_zero") for p in (0, 1)]
+word_split_name = lambda which, poly: f"word_split_{which}_{'mask' if poly == 0 else 'body'}"  # noqa: E731
+
+
 # ---- the sets --------------------------------------------------------------------------------------
 def cases(level, dk):
     """name -> (lwe, acc0): the whole set of one level."""
@@ -335,6 +377,10 @@ def cases(level, dk):
     out["steps_0_1"] = boundary_case(L, 0, {0: L.N, 1: 3})
     out["steps_0_5"] = boundary_case(L, 0, {0: L.N + 1, 5: L.N})
     out["step_last"] = boundary_case(L, 0, {L.last_step: L.N})
+    if level == 2:  # the two-CU kernels' schedule and their split of the digits over groups and workgroups
+        out["steps_many"] = boundary_case(L, 0, STEPS_MANY(L))
+        for which, poly in WORD_SPLIT:
+            out[word_split_name(which, poly)] = word_split_case(L, which, poly)
     return out
 
 

@@ -110,10 +110,10 @@ def test_one_step_on_sparse_accumulator_matches_bigint(orc, dk, level, a_kind):
 @pytest.mark.parametrize("level", [1, 2])
 def test_every_acc0_is_canonical(sets, level):
     L = AC.LEVELS[level]
-    assert 12 <= len(sets[level]) <= 16
+    assert len(sets[level]) == (14 if level == 1 else 19)
     for name, (lwe, acc0) in sets[level].items():
         assert acc0.shape == (2, L.N) and acc0.dtype == np.uint64 and int(acc0.max()) < L.q, name
-        assert np.count_nonzero(lwe[:L.n_lwe]) in (1, 2), name
+        assert np.count_nonzero(lwe[:L.n_lwe]) in ((6,) if name == "steps_many" else (1, 2)), name
 
 
 def test_trace_inputs_are_canonical(tsets):
@@ -197,6 +197,49 @@ def test_multi_step_cases(sets):
         nz = lambda name: [int(i) for i in np.flatnonzero(sets[level][name][0][:L.n_lwe])]  # noqa: E731
         assert nz("steps_0_1") == [0, 1] and nz("steps_0_5") == [0, 5] and nz("step_last") == [L.last_step]
     assert AC.L1.last_step == 511 and AC.L2.last_step == 669
+
+
+def test_steps_many_runs_six_steps_of_every_kind(sets, orc):
+    """Level 2's steps_many: boundary targets at its first step, and executed steps (nonzero a_i) that hold two
+    consecutive steps, a gap, and the last two steps 668 and 669 -- at least six after step 0 counts as the
+    first, so each parity of the executed-step count comes up three times."""
+    L = AC.L2
+    lwe, acc0 = sets[2]["steps_many"]
+    steps = [int(i) for i in np.flatnonzero(lwe[:L.n_lwe])]
+    assert steps == [0, 1, 2, 7, 668, 669] and len(steps) >= 6
+    assert all(0 < int(lwe[i]) < 2 * L.N for i in steps) and int(lwe[0]) == L.N
+    assert {int(lwe[i]) for i in steps} >= {L.N, 2 * L.N - 1, 1}, "a = N, a wrap-around amount and a = 1"
+    gaps = [b - a for a, b in zip(steps, steps[1:])]
+    assert gaps[:2] == [1, 1] and gaps[2] > 1 and gaps[-1] == 1 and steps[-1] == L.last_step == L.n_lwe - 1
+    # its first step decomposes the boundary case's inputs
+    assert np.array_equal(acc0, sets[2]["boundary"][1])
+    # every one of the six is executed by the oracle: without any one of them the output differs
+    full = orc.br2_from(lwe, acc0)
+    for i in steps:
+        fewer = lwe.copy()
+        fewer[i] = 0
+        assert not np.array_equal(orc.br2_from(fewer, acc0), full), i
+
+
+def test_word_split_cases_hold_what_they_claim(sets):
+    """Each word_split case: one step with a = N; every coefficient of the named polynomial decomposes (the
+    oracle's decomposition) to three zero digits beside three digits at one sign's extremes, both signs
+    present, and the other polynomial and all of its digits are zero."""
+    L = AC.L2
+    B, (tmin, tmax) = L.B, AC.top_range(L)
+    dg = AC.word_split_digits(L)
+    assert dg["high_zero"] == ([B // 2 - 1] * 3 + [0] * 3, [-(B // 2)] * 3 + [0] * 3)
+    lp, ln = dg["low_zero"]
+    assert lp[:5] == [0, 0, 0, B // 2 - 1, B // 2 - 1] and ln[:5] == [0, 0, 0, -(B // 2), -(B // 2)]
+    # the top digit is the largest of its sign that fits: one more leaves +-h
+    assert 0 < lp[5] <= tmax and AC.from_digits(L, lp[:5] + [lp[5] + 1]) > L.h
+    assert tmin <= ln[5] < 0 and AC.from_digits(L, ln[:5] + [ln[5] - 1]) < -L.h
+    for which, poly in AC.WORD_SPLIT:
+        lwe, acc0 = sets[2][AC.word_split_name(which, poly)]
+        assert AC.first_step(L, lwe) == (0, L.N) and np.count_nonzero(lwe[:L.n_lwe]) == 1
+        assert not acc0[1 - poly].any() and not AC.step_input(L, acc0[1 - poly], L.N).any()
+        seen = {tuple(AC.decompose(L, v)) for v in AC.step_input(L, acc0[poly], L.N)}
+        assert seen == {tuple(dg[which][0]), tuple(dg[which][1])}, (which, poly)
 
 
 def _digit_spectra(L, values, m):

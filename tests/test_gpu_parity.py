@@ -105,6 +105,12 @@ def real():
     orc.close()
 
 
+def _since(det, before):
+    """The launch record's counters that moved since `before` (a det.launch_record()): name -> launches."""
+    now = det.launch_record()
+    return {k: now[k] - before[k] for k in now if now[k] != before[k]}
+
+
 @pytest.fixture(params=["latency", "throughput"])
 def path(request, real):
     """Both kernel families on the same small inputs: the latency kernels (chunks up to 64
@@ -155,10 +161,14 @@ def test_latency_level2_variants_match_throughput(real):
         mask[::9] = True
         ca, cb = PL.mixed_clues(mask, seed=900 + n)
         det.set_latency_threshold(threshold)
+        before = det.launch_record()
         try:
             lat = det.detect_batch(ca, cb)
         finally:
             det.set_latency_threshold(0)
+        # 64 messages: the two-CU kernel (128 workers, no helper rows); 130: 260 workers do not fit, br2l
+        # with the one-workgroup trace
+        assert _since(det, before) == ({"br2y": 1, "trace_x": 1} if n == 64 else {"br2l": 1, "trace_kernel": 1})
         thr = det.detect_batch(ca, cb)
         det.set_latency_threshold(64)
         assert np.array_equal(lat, thr)
@@ -192,12 +202,19 @@ def test_latency_level2_fft_two_cu_matches_ntt(real, monkeypatch):
             mask[::5] = True
             ca, cb = PL.mixed_clues(mask, seed=1200 + n)
             fl = fft.first_level(ca, cb)
+            rec = {d: d.launch_record() for d in (fft, ntt, nopf, slow)}
             want = ntt.blind_rotate_level2(fl)
             assert np.array_equal(fft.blind_rotate_level2(fl), want), n
             assert np.array_equal(fft.second_level(fl), ntt.second_level(fl)), n
+            # the rotation and the rotation + trace: both sides ran their two-CU kernel, not br2l twice
+            assert _since(ntt, rec[ntt]) == {"br2x": 2, "trace_x": 1}, n
+            assert _since(fft, rec[fft]) == ({"br2y": 2, "br2y_helpers": 2, "trace_x": 1} if n < 64
+                                             else {"br2y": 2, "trace_x": 1}), n
             if n == 7:
                 assert np.array_equal(nopf.blind_rotate_level2(fl), want)
                 assert np.array_equal(slow.blind_rotate_level2(fl), want)
+                assert _since(nopf, rec[nopf]) == {"br2y": 1}
+                assert _since(slow, rec[slow]) == {"br2y": 1, "br2y_helpers": 1}
     finally:
         ntt.close()
         nopf.close()

@@ -52,6 +52,20 @@ def test_every_header_function_bound_with_same_shape():
         assert h[name] == r[name], f"{name}: header {h[name]} vs crate {r[name]}"
 
 
+def test_launch_kinds_agree():
+    """omr_launch_kind's indices in the header, the crate's OMR_LAUNCH_* constants and the Python mirror's
+    LAUNCH_KINDS: the same names at the same indices, OMR_LAUNCH_COUNT of them."""
+    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
+    body = re.search(r"typedef enum \{([^{}]*)\}\s*omr_launch_kind;", text).group(1)
+    c = {m.group(1): int(m.group(2)) for m in re.finditer(r"OMR_LAUNCH_(\w+)\s*=\s*(\d+)", body)}
+    r = {m.group(1): int(m.group(2))
+         for m in re.finditer(r"pub const OMR_LAUNCH_(\w+): usize = (\d+);", open(LIB).read())}
+    assert c == r and c.pop("COUNT") == len(c) and sorted(c.values()) == list(range(len(c)))
+    src = open(os.path.join(ROOT, "tfhe-omr_amd", "omr_amd.py")).read()
+    kinds = re.findall(r'"(\w+)"', re.search(r"LAUNCH_KINDS = \((.*?)\)", src, flags=re.S).group(1))
+    assert [k.upper() for k in kinds] == sorted(c, key=c.get)
+
+
 @pytest.mark.parametrize("c_name,rust_name", [("omr_retrieval_params", "OmrRetrievalParams"),
                                               ("omr_detection_key_view", "OmrDetectionKeyView"),
                                               ("omr_detect_timing", "OmrDetectTiming")])

@@ -2,6 +2,7 @@
 // outside csrc/ includes this), and the few functions those units lend each other. By owner:
 //   context.hip   creation and destruction, key conversion and bounds, setters and getters, scratch sizes
 //   detect.hip    every rotation, key-switch and trace launch, detect on device and host buffers, timing
+//   two_cu_from.hip  br2y_from_kernel / br2x_from_kernel alone (no host code but their launch pointers)
 //   coalesce.hip  omr_detect's queue
 //   encode.hip    the encode kernels' launches and entry points
 //   digest.hip    the digest session over detect and encode
@@ -106,6 +107,10 @@ struct omr_ctx {
     double apriori_t = 1.0, apriori_y = 1.0;
     bool trace_fft = false;
   } ex;
+
+  // The launch record (omr_ctx_launch_record): cumulative launches per omr_launch_kind, counted on the
+  // host where detect.hip chooses the kernel. No device state.
+  uint64_t launches[OMR_LAUNCH_COUNT] = {};
 
   // Stage timing. mode 0: off; 1 or 2: detect_device records EV_PER_CHUNK events per chunk, and
   // messages / chunks describe the last timed call. omr_detect_batch stages the host input in pieces

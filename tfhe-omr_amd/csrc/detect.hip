@@ -17,6 +17,7 @@
 #include "br2_ntt.hpp"
 #include "ctx.hpp"
 #include "ks_mfma.hpp"
+#include "two_cu_from.hpp"
 
 using namespace omr;
 
@@ -58,6 +59,9 @@ __global__ void guard_fold_kernel(unsigned long long *words, int level, double t
 namespace {
 
 bool latency_path(const omr_ctx *c, size_t n) { return n <= c->latency_max; }
+
+// The launch record (omr_ctx_launch_record): one more launch of `kind`, where the choice is made.
+void note_launch(omr_ctx *c, omr_launch_kind kind) { ++c->launches[kind]; }
 
 // Zero the per-launch guard word of `level` before a guarded launch.
 omr_status guard_begin(omr_ctx *c, int level, hipStream_t st) {
@@ -176,9 +180,10 @@ omr_status handoff_scratch(omr_ctx *c, DevBuf<double> &slots, size_t nslots, Dev
 
 // The latency path's level-2 rotation over two CUs per message as a cooperative launch: br2y_kernel
 // or br2x_kernel over 2 n workgroups; *launched stays false when it does not fit or is refused, so
-// the caller falls back to br2l_kernel.
+// the caller falls back to br2l_kernel. acc0 (optional): the same choice, grid and arguments on
+// br2y_from_kernel / br2x_from_kernel (two_cu_from.hip), which take acc0 as one more argument.
 omr_status launch_br2xy(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t *out, hipStream_t st,
-                        bool *launched) {
+                        bool *launched, const uint64_t *acc0) {
   omr_ctx::Handoff &h = c->ho;
   *launched = false;
   if (!h.coop || 2 * n > (size_t)h.num_cu) return OMR_OK;  // one 150 KB-LDS workgroup per CU
@@ -190,7 +195,7 @@ omr_status launch_br2xy(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t 
   uint32_t *flags = h.x_flags;
   int *err = h.x_err;
   void *args[] = {(void *)&lwe_int, (void *)&bsk2, (void *)&tb, (void *)&slots, (void *)&flags, (void *)&err,
-                  (void *)&out};
+                  (void *)&out, (void *)&acc0};
   // br2y_kernel (FFT) when the bound of its accumulation order proves it exact and level 2 is not
   // guarded; br2x_kernel's exact NTT otherwise (same arguments apart from the key form)
   const bool y = h.br2y && !guarded(c, 1) && c->ex.apriori_y < 0.5;
@@ -202,10 +207,18 @@ omr_status launch_br2xy(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t 
   const int rows = (size_t)w8 * (2 + 2 * BR2Y_H) <= (size_t)h.num_cu && !h.no_prefetch ? 2 + 2 * BR2Y_H : 2;
   if (y && (size_t)w8 * rows > (size_t)h.num_cu) return OMR_OK;  // one workgroup per CU: br2l instead
   void *args_y[] = {(void *)&lwe_int, (void *)&bskf, (void *)&twg, (void *)&tb, (void *)&slots, (void *)&flags,
-                    (void *)&err, (void *)&out, (void *)&nmsg, (void *)&w8, (void *)&allow_fast};
-  const void *kern = y ? reinterpret_cast<const void *>(&br2y_kernel) : reinterpret_cast<const void *>(&br2x_kernel);
-  return coop_launch(c, "br2x", kern, dim3(y ? (unsigned)(w8 * rows) : (unsigned)(2 * n)), dim3(y ? BR2Y_T : BR2L_T),
-                     y ? args_y : args, st, launched);
+                    (void *)&err, (void *)&out, (void *)&nmsg, (void *)&w8, (void *)&allow_fast, (void *)&acc0};
+  // (the production kernels take the arguments before acc0)
+  const void *kern = acc0 ? (y ? br2y_from_kernel_ptr() : br2x_from_kernel_ptr())
+                          : (y ? reinterpret_cast<const void *>(&br2y_kernel)
+                               : reinterpret_cast<const void *>(&br2x_kernel));
+  OMR_TRY(coop_launch(c, "br2x", kern, dim3(y ? (unsigned)(w8 * rows) : (unsigned)(2 * n)), dim3(y ? BR2Y_T : BR2L_T),
+                      y ? args_y : args, st, launched));
+  if (*launched) {
+    note_launch(c, y ? OMR_LAUNCH_BR2Y : OMR_LAUNCH_BR2X);
+    if (y && rows > 2) note_launch(c, OMR_LAUNCH_BR2Y_HELPERS);
+  }
+  return OMR_OK;
 }
 
 // The latency path's trace over TRACE_X CUs per message (trace_x_kernel) as a cooperative launch;
@@ -234,14 +247,21 @@ omr_status launch_trace(omr_ctx *c, size_t n, uint64_t *out, hipStream_t st, boo
   const double2 *fft2 = c->tab.fft2;
   bool multi = false;
   if (lat) OMR_TRY(launch_trace_x(c, n, out, st, &multi));
+  omr_launch_kind kind = OMR_LAUNCH_TRACE_X;
   if (lat || !c->ex.trace_fft) {
-    if (!multi) trace_kernel<<<(unsigned)n, BR2_T, 0, st>>>(out, k.tk, tb);
+    if (!multi) {
+      trace_kernel<<<(unsigned)n, BR2_T, 0, st>>>(out, k.tk, tb);
+      kind = OMR_LAUNCH_TRACE_KERNEL;
+    }
   } else if (g) {
     trace_fft_guard_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(out, k.tkf, fft2, tb, c->ex.margin + 3);
+    kind = OMR_LAUNCH_TRACE_FFT_GUARD;
   } else {
     trace_fft_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(out, k.tkf, fft2, tb);
+    kind = OMR_LAUNCH_TRACE_FFT;
   }
   HIP_TRY(hipGetLastError());
+  note_launch(c, kind);
   return OMR_OK;
 }
 
@@ -251,7 +271,9 @@ omr_status launch_trace(omr_ctx *c, size_t n, uint64_t *out, hipStream_t st, boo
 // pair notes both kernels' rounding margins in level 2's word, and a pair whose margin reaches the
 // threshold is re-run on the exact NTT (every workgroup of the fallbacks leaves at once otherwise).
 // acc0 (the test entry omr_blind_rotate_level2_from): the initial accumulators (device, canonical
-// u64 [n][2][N2]); the same selection, on each kernel's _from instantiation.
+// u64 [n][2][N2]); the same selection, on each kernel's _from instantiation -- on the latency path the
+// two-CU br2y_from_kernel / br2x_from_kernel, and br2l_from_kernel only where br2l_kernel would run
+// (the cooperative launch does not fit or is refused).
 omr_status launch_br2(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t *out, int mode, hipStream_t st,
                       hipEvent_t mid = nullptr, const uint64_t *acc0 = nullptr) {
   const omr_ctx::Keys &k = c->keys;
@@ -261,28 +283,34 @@ omr_status launch_br2(omr_ctx *c, size_t n, const uint32_t *lwe_int, uint64_t *o
   const bool lat = latency_path(c, n), g = !lat && guarded(c, 1);
   if (lat) {
     bool two_cu = false;
-    // (the two-CU kernels br2x / br2y take no acc0: with the override their existing code did not
-    // compile unchanged, so an override on the latency path runs the one-workgroup kernel)
-    if (!acc0) OMR_TRY(launch_br2xy(c, n, lwe_int, out, st, &two_cu));
-    if (acc0)
-      br2l_from_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, nullptr, 0.0, acc0);
-    else if (!two_cu)
-      br2l_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out);
+    OMR_TRY(launch_br2xy(c, n, lwe_int, out, st, &two_cu, acc0));  // notes br2y / br2x when it launched
+    if (!two_cu) {
+      if (acc0)
+        br2l_from_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, nullptr, 0.0, acc0);
+      else
+        br2l_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out);
+      note_launch(c, OMR_LAUNCH_BR2L);
+    }
   } else if (g) {
+    note_launch(c, OMR_LAUNCH_BR2F_GUARD);
     OMR_TRY(guard_begin(c, 1, st));
     if (acc0)
       br2f_guard_from_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, word, acc0);
     else
       br2f_guard_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, word);
-  } else if (acc0) {
-    br2f_from_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, acc0);
   } else {
-    br2f_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out);
+    note_launch(c, OMR_LAUNCH_BR2F);
+    if (acc0)
+      br2f_from_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out, acc0);
+    else
+      br2f_kernel<<<(unsigned)n, Fft1024::T, 0, st>>>(lwe_int, k.bsk2f, fft2, tb, out);
   }
+  if (acc0) note_launch(c, OMR_LAUNCH_BR2_FROM);
   HIP_TRY(hipGetLastError());
   if (mid) HIP_TRY(hipEventRecord(mid, st));
   if (mode == 0) OMR_TRY(launch_trace(c, n, out, st, lat, g));
   if (!g) return OMR_OK;
+  note_launch(c, OMR_LAUNCH_GUARD_FALLBACK);
   if (acc0)
     br2l_from_kernel<<<(unsigned)n, BR2L_T, 0, st>>>(lwe_int, k.bsk2, tb, out, word, c->ex.thr[1], acc0);
   else
@@ -304,6 +332,7 @@ omr_status launch_trace_only(omr_ctx *c, size_t n, uint64_t *io, uint64_t *saved
   }
   OMR_TRY(launch_trace(c, n, io, st, lat, g));
   if (!g) return OMR_OK;
+  note_launch(c, OMR_LAUNCH_GUARD_FALLBACK);
   trace_restore_kernel<<<(unsigned)n, BR2_T, 0, st>>>(io, saved, c->ex.margin + 3, c->ex.thr[1]);
   HIP_TRY(hipGetLastError());
   trace_fallback_kernel<<<(unsigned)n, BR2_T, 0, st>>>(io, c->keys.tk, c->tab.tb, c->ex.margin + 3, c->ex.thr[1]);
@@ -653,6 +682,13 @@ extern "C" omr_status omr_trace(omr_ctx *c, const uint64_t *rlwe, size_t n, uint
   HIP_TRY(hipStreamSynchronize(c->stream));
   OMR_TRY(take_handoff_error(c));
   HIP_TRY(hipMemcpy(out, dio, n * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_ctx_launch_record(omr_ctx *c, uint64_t counts[OMR_LAUNCH_COUNT]) {
+  if (!c || !counts) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_ctx_launch_record: NULL argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::copy(c->launches, c->launches + OMR_LAUNCH_COUNT, counts);
   return OMR_OK;
 }
 

@@ -87,6 +87,10 @@ class _KeyAuditSummary(C.Structure):
                [("noise_bits", C.c_uint64 * 50)]
 
 
+# omr_launch_kind, in index order (omr_ctx_launch_record)
+LAUNCH_KINDS = ("br2f", "br2f_guard", "br2l", "br2x", "br2y", "br2y_helpers", "br2_from", "guard_fallback",
+                "trace_fft", "trace_fft_guard", "trace_x", "trace_kernel")
+
 # omr_ct_audit as a structured dtype (16 bytes)
 AUDIT_RECORD = np.dtype([("max_abs_residual", np.uint64), ("nonzero", np.uint32), ("first", np.uint32)])
 AUDIT_RESIDUAL_BINS = 50
@@ -151,6 +155,7 @@ EXPORTS = {
     "omr_ctx_set_rounding_guard": (C.c_int, [C.c_void_p, C.c_int]),
     "omr_ctx_rounding_margin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "omr_ctx_exactness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "omr_ctx_launch_record": (C.c_int, [C.c_void_p, C.c_void_p]),
     "omr_fft_twiddles_dd": (C.c_int, [C.c_int, np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")]),
     "omr_ctx_key_spectrum": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t,
                                        np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")]),
@@ -1232,6 +1237,13 @@ class Detector:
         g, b = (C.c_int * 2)(), (C.c_uint64 * 2)()
         _check(lib().omr_ctx_exactness(self._h, g, b), "omr_ctx_exactness")
         return {"guarded": [bool(v) for v in g], "breaches": list(b)}
+
+    def launch_record(self) -> dict:
+        """Cumulative launches per level-2 rotation / trace kernel since creation (omr_ctx_launch_record):
+        LAUNCH_KINDS name -> count. Host counters; compare two reads."""
+        counts = (C.c_uint64 * len(LAUNCH_KINDS))()
+        _check(lib().omr_ctx_launch_record(self._h, counts), "omr_ctx_launch_record")
+        return dict(zip(LAUNCH_KINDS, (int(v) for v in counts)))
 
     def key_spectrum(self, level: int, first: int, count: int) -> np.ndarray:
         """Stored key-spectrum values [count] complex (omr_ctx_key_spectrum)."""
