@@ -833,6 +833,97 @@ omr_status omr_auditor_decode_digest_indexed(omr_auditor *aud, const void *idx_c
                                              size_t *found, uint16_t *payloads, omr_audit_summary *summary);
 
 /* ---------------------------------------------------------------------------------------
+ * Reference payload weights by seek (none in the reference): omr_payload_weights' own values, weight by
+ * weight, without the table. The reference draws one StdRng stream through Uniform<u16>(0, 257)
+ * (detector.rs:376-387), which rejects a 32-bit word v when the low half of v * 257 exceeds the zone
+ * 0xFFFFFFFE. Since 2^32 = 1 (mod 257), v * 257 = 0xFFFFFFFF (mod 2^32) has the single solution
+ * v = 0x00FF00FF: one word in 2^32 is rejected, and accepted draw n sits at raw stream position
+ * n + (rejections met so far). A 2^20 x 1,005 board (1.05e9 draws) meets at least one rejection with
+ * probability 0.22, so the list of rejections is short but cannot be assumed empty.
+ *
+ * Definition. The stream is ChaCha12 with key[0..7] the little-endian words of the 32-byte seed, stream
+ * id 0: word(r) = chacha_block(12, key, counter = r >> 4, stream = 0)[r & 15] for raw position r. A raw word
+ * is rejected when (uint32_t)(word * 257) > zone. With r_0 < r_1 < .. the rejected raw positions:
+ *   at[k]  = r_k - k                        draws accepted when rejection k is met (nondecreasing)
+ *   pos(n) = n + #{k : at[k] <= n}          raw position of accepted draw n
+ *   w(n)   = (uint64_t)word(pos(n)) * 257 >> 32
+ * and weight (j, i) of a board is w(j * all + i) for j < combination_count, 0 for a padding combination.
+ * Two adjacent rejected words give two equal entries of at[]. A seek lists the rejections that matter for
+ * the draws n < draws: those with at[k] < draws, a prefix of the list. A board needs
+ * draws >= combination_count * all; every consumer returns OMR_ERR_INVALID_ARGUMENT otherwise. Only the
+ * builders read `zone`; consumers read draws, n and at[] alone. At most OMR_WEIGHT_SEEK_MAX rejections
+ * fit: a stream with more is OMR_ERR_INVALID_ARGUMENT ("more than 32 rejections: use the table") from the
+ * builders, which then leave *out untouched; with the reference's zone a board expects draws / 2^32 rejections, 0.24 at
+ * 2^20 x 1,005 (33 of them: below 1e-50), and the cap is reached around 2^37 draws. The indexed convention above stays: it needs no scan and has no cap, where nobody is bound
+ * to the reference's stream.
+ * ------------------------------------------------------------------------------------- */
+#define OMR_WEIGHT_SEEK_MAX 32
+#define OMR_WEIGHT_ZONE 0xFFFFFFFEu
+typedef struct {
+  uint64_t draws;                   /* valid for accepted draws n < draws */
+  uint32_t n;                       /* rejections that matter for those draws */
+  uint32_t zone;                    /* 0xFFFFFFFE for every public builder */
+  uint64_t at[OMR_WEIGHT_SEEK_MAX]; /* at[k] = r_k - k, nondecreasing */
+} omr_weight_seek;
+/* Host builder, parallel over ChaCha blocks (nthreads <= 0: the host's cores, at most 16): scans the raw
+ * words [0, draws + OMR_WEIGHT_SEEK_MAX], which hold every rejection that can shift a draw below `draws`.
+ * OMR_ERR_INVALID_ARGUMENT for NULL or draws >= 2^62. */
+omr_status omr_weight_seek_build_cpu(const uint8_t seed[32], uint64_t draws, int nthreads, omr_weight_seek *out);
+/* The same scan on the current HIP device, on hip_stream (NULL = null stream); returns after the stream
+ * has completed the scan, as omr_gen_clues_device does. The same result and the same errors. */
+omr_status omr_weight_seek_build_device(const uint8_t seed[32], uint64_t draws, omr_weight_seek *out,
+                                        void *hip_stream);
+/* Stage entries for tests: the builders with an explicit zone (a smaller zone makes rejections frequent).
+ * The public builders are these with OMR_WEIGHT_ZONE. */
+omr_status omr_weight_seek_build_zone_cpu(const uint8_t seed[32], uint64_t draws, uint32_t zone, int nthreads,
+                                          omr_weight_seek *out);
+omr_status omr_weight_seek_build_zone_device(const uint8_t seed[32], uint64_t draws, uint32_t zone,
+                                             omr_weight_seek *out, void *hip_stream);
+/* The recipient's matrix in the reference's convention, host, parallel: out u16 [n_combos][n_indices],
+ * out[r][k] = weight (first_combo + r, indices[k]); rows at or beyond combination_count are zero (the layout
+ * and padding of omr_indexed_weights_at). OMR_ERR_INVALID_ARGUMENT for NULL, an index >= all, seek->n above
+ * OMR_WEIGHT_SEEK_MAX, or combination_count * all > seek->draws. */
+omr_status omr_payload_weights_at(const uint8_t seed[32], size_t all_payloads_count, uint32_t combination_count,
+                                  const omr_weight_seek *seek, uint32_t first_combo, uint32_t n_combos,
+                                  const size_t *indices, size_t n_indices, uint16_t *out, int nthreads);
+/* omr_encode_payloads_indexed_device with the reference's weights found through the seek: the same
+ * arguments, checks and padding rules, and the same bits as omr_encode_payloads_device fed
+ * omr_payload_weights' table. Also OMR_ERR_INVALID_ARGUMENT for seek = NULL, seek->n above
+ * OMR_WEIGHT_SEEK_MAX, or combination_count * all_payloads_count > seek->draws. */
+omr_status omr_encode_payloads_seek_device(omr_ctx *ctx, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D,
+                                           size_t global_offset, size_t all_payloads_count, const uint8_t seed[32],
+                                           const omr_weight_seek *seek, uint32_t combination_count,
+                                           uint32_t first_ct, uint32_t n_ct, uint32_t cmb_per_ct,
+                                           uint64_t *d_out /* [n_ct][2][2048] */, void *hip_stream);
+/* The same on host buffers; returns when done. */
+omr_status omr_encode_payloads_seek(omr_ctx *ctx, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                    size_t global_offset, size_t all_payloads_count, const uint8_t seed[32],
+                                    const omr_weight_seek *seek, uint32_t combination_count, uint32_t first_ct,
+                                    uint32_t n_ct, uint32_t cmb_per_ct, uint64_t *out);
+/* omr_digest_begin without the table: the session builds the seek of its board on the context's device at
+ * begin (omr_weight_seek_build_device; the call returns when the scan is done), holds no weights
+ * (omr_digest_device_bytes: weights = 0) and runs the seek kernel per piece. Every other session call
+ * behaves as documented above, and the digest is bit-identical to that of an omr_digest_begin session on
+ * the same inputs. */
+omr_status omr_digest_begin_seek(omr_ctx *ctx, size_t all_payloads_count, size_t pertinent_count,
+                                 uint64_t index_seed, const uint8_t weight_seed[32], void *hip_stream,
+                                 omr_digest **out);
+/* omr_retrieve_payloads without the table: the matrix from omr_payload_weights_at. seek = NULL builds the
+ * seek inside the call (omr_weight_seek_build_cpu). The same bits and status codes as omr_retrieve_payloads
+ * given omr_payload_weights' table, OMR_ERR_NOT_INVERTIBLE included. */
+omr_status omr_retrieve_payloads_seek(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
+                                      size_t all_payloads_count, uint32_t combination_count,
+                                      const uint8_t weight_seed[32], const omr_weight_seek *seek,
+                                      const size_t *indices, size_t n_indices, uint16_t *payloads);
+/* The same on the auditor (see "Retrieval on the auditor": full or compact ciphertexts, the same `bits`
+ * rule): the matrix is built on the device from the same statement; seek = NULL builds the seek on the
+ * auditor's device. */
+omr_status omr_auditor_retrieve_payloads_seek(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
+                                              size_t all_payloads_count, uint32_t combination_count,
+                                              const uint8_t weight_seed[32], const omr_weight_seek *seek,
+                                              const size_t *indices, size_t n_indices, uint16_t *payloads);
+
+/* ---------------------------------------------------------------------------------------
  * Key audit (none in the reference): check a detection key against its secret before it is uploaded and
  * after any reload, and count non-canonical words at intake without a secret. A detector runs to
  * completion on a damaged key and returns well-formed ciphertexts that decrypt to "not pertinent"; this

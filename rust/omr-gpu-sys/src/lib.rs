@@ -123,6 +123,17 @@ pub mod ffi {
         pub messages: usize,
         pub pv_capacity_messages: usize,
     }
+    /// `OMR_WEIGHT_SEEK_MAX`: the rejections an `omr_weight_seek` holds.
+    pub const OMR_WEIGHT_SEEK_MAX: usize = 32;
+    /// `omr_weight_seek` (include/omr_gpu.h, "Reference payload weights by seek").
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct OmrWeightSeek {
+        pub draws: u64,
+        pub n: u32,
+        pub zone: u32,
+        pub at: [u64; OMR_WEIGHT_SEEK_MAX],
+    }
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
     pub struct OmrRetrievalParams {
@@ -414,6 +425,41 @@ pub mod ffi {
                                                  found: *mut usize, payloads: *mut u16,
                                                  summary: *mut OmrAuditSummary) -> OmrStatus;
 
+        // reference payload weights by seek (none in the reference)
+        pub fn omr_weight_seek_build_cpu(seed: *const u8, draws: u64, nthreads: c_int,
+                                         out: *mut OmrWeightSeek) -> OmrStatus;
+        pub fn omr_weight_seek_build_device(seed: *const u8, draws: u64, out: *mut OmrWeightSeek,
+                                            hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_weight_seek_build_zone_cpu(seed: *const u8, draws: u64, zone: u32, nthreads: c_int,
+                                              out: *mut OmrWeightSeek) -> OmrStatus;
+        pub fn omr_weight_seek_build_zone_device(seed: *const u8, draws: u64, zone: u32, out: *mut OmrWeightSeek,
+                                                 hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_payload_weights_at(seed: *const u8, all_payloads_count: usize, combination_count: u32,
+                                      seek: *const OmrWeightSeek, first_combo: u32, n_combos: u32,
+                                      indices: *const usize, n_indices: usize, out: *mut u16,
+                                      nthreads: c_int) -> OmrStatus;
+        pub fn omr_encode_payloads_seek_device(ctx: *mut OmrCtx, d_pv: *const u64, d_payloads: *const u16, d: usize,
+                                               global_offset: usize, all_payloads_count: usize, seed: *const u8,
+                                               seek: *const OmrWeightSeek, combination_count: u32, first_ct: u32,
+                                               n_ct: u32, cmb_per_ct: u32, d_out: *mut u64,
+                                               hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_encode_payloads_seek(ctx: *mut OmrCtx, pv: *const u64, payloads: *const u16, d: usize,
+                                        global_offset: usize, all_payloads_count: usize, seed: *const u8,
+                                        seek: *const OmrWeightSeek, combination_count: u32, first_ct: u32,
+                                        n_ct: u32, cmb_per_ct: u32, out: *mut u64) -> OmrStatus;
+        pub fn omr_digest_begin_seek(ctx: *mut OmrCtx, all_payloads_count: usize, pertinent_count: usize,
+                                     index_seed: u64, weight_seed: *const u8, hip_stream: *mut c_void,
+                                     out: *mut *mut OmrDigest) -> OmrStatus;
+        pub fn omr_retrieve_payloads_seek(sk: *const OmrSecretKeyPack, pay_cts: *const u64, n_ct: u32,
+                                          all_payloads_count: usize, combination_count: u32,
+                                          weight_seed: *const u8, seek: *const OmrWeightSeek,
+                                          indices: *const usize, n_indices: usize, payloads: *mut u16) -> OmrStatus;
+        pub fn omr_auditor_retrieve_payloads_seek(aud: *mut OmrAuditor, pay_cts: *const c_void, n_ct: u32,
+                                                  bits: c_int, all_payloads_count: usize, combination_count: u32,
+                                                  weight_seed: *const u8, seek: *const OmrWeightSeek,
+                                                  indices: *const usize, n_indices: usize,
+                                                  payloads: *mut u16) -> OmrStatus;
+
         // stage entry points (benches/two_level_bs.rs)
         pub fn omr_first_level(ctx: *mut OmrCtx, clue_a: *const u16, clue_b: *const u16, d: usize,
                                lwe_int: *mut u32) -> OmrStatus;
@@ -549,6 +595,34 @@ pub fn indexed_weights_table(seed: &[u8; 32], rp: &RetrievalParams) -> Result<Ve
     check(unsafe {
         omr_indexed_weights_table(seed.as_ptr(), rp.all_payloads_count, l.combination_count, l.cmb_cipher_count,
                                   l.cmb_count_per_cipher, out.as_mut_ptr(), 0)
+    })?;
+    Ok(out)
+}
+
+/// The seek of a board's payload weights (`omr_weight_seek_build_cpu`, or `_device` on the current HIP
+/// device): the rejections of the reference's stream within the board's `combination_count * all` draws.
+/// With it, `payload_weights`' values are found weight by weight and nobody draws the table.
+pub fn weight_seek(seed: &[u8; 32], rp: &RetrievalParams, on_device: bool) -> Result<OmrWeightSeek, OmrError> {
+    let draws = rp.layout.combination_count as u64 * rp.all_payloads_count as u64;
+    let mut out = OmrWeightSeek::default();
+    check(unsafe {
+        if on_device {
+            omr_weight_seek_build_device(seed.as_ptr(), draws, &mut out, std::ptr::null_mut())
+        } else {
+            omr_weight_seek_build_cpu(seed.as_ptr(), draws, 0, &mut out)
+        }
+    })?;
+    Ok(out)
+}
+
+/// The recipient's matrix in the reference's convention (`omr_payload_weights_at`): `[n_combos][indices.len()]`,
+/// `payload_weights`' weight of combination `first_combo + r` for the message `indices[k]`, through the seek.
+pub fn payload_weights_at(seed: &[u8; 32], rp: &RetrievalParams, seek: &OmrWeightSeek, first_combo: u32,
+                          n_combos: u32, indices: &[usize]) -> Result<Vec<u16>, OmrError> {
+    let mut out = vec![0u16; n_combos as usize * indices.len()];
+    check(unsafe {
+        omr_payload_weights_at(seed.as_ptr(), rp.all_payloads_count, rp.layout.combination_count, seek, first_combo,
+                               n_combos, indices.as_ptr(), indices.len(), out.as_mut_ptr(), 0)
     })?;
     Ok(out)
 }
@@ -1003,6 +1077,19 @@ impl GpuDetector {
         })?;
         Ok(DigestSession { raw, _detector: self })
     }
+
+    /// `omr_digest_begin_seek`: the default session's digest without its weight table. The session scans the
+    /// reference's stream for its rejections on the device at begin; `Retriever::decode_digest` or
+    /// `decode_digest_seek` retrieves it.
+    pub fn digest_session_seek(&self, rp: &RetrievalParams, index_seed: u64,
+                               weight_seed: &[u8; 32]) -> Result<DigestSession<'_>, OmrError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe {
+            omr_digest_begin_seek(self.ctx, rp.all_payloads_count, rp.pertinent_count, index_seed,
+                                  weight_seed.as_ptr(), std::ptr::null_mut(), &mut raw)
+        })?;
+        Ok(DigestSession { raw, _detector: self })
+    }
 }
 
 impl DigestSession<'_> {
@@ -1255,6 +1342,38 @@ impl<'a> Retriever<'a> {
             omr_retrieve_payloads_indexed(self.secret.raw, pay.as_ptr(), payloads_digest.len() as u32,
                                           rp.all_payloads_count, rp.layout.combination_count, seed.as_ptr(),
                                           found_buf.as_ptr(), found_buf.len(), out.as_mut_ptr())
+        })?;
+        let payloads = out
+            .chunks_exact(OMR_PAYLOAD_LEN)
+            .map(|c| {
+                let mut p = [0u16; OMR_PAYLOAD_LEN];
+                p.copy_from_slice(c);
+                p
+            })
+            .collect();
+        Ok((found_buf, payloads))
+    }
+
+    /// `decode_digest` without the weight table (`omr_retrieve_payloads_seek`): the reference's weights of
+    /// the indices found, through `seek` or, with `None`, a seek built inside the call.
+    pub fn decode_digest_seek(&self, indices_digest: &[NttRlwe], payloads_digest: &[NttRlwe], seed: &[u8; 32],
+                              seek: Option<&OmrWeightSeek>) -> Result<(Vec<usize>, Vec<Payload>), OmrError> {
+        let rp = self.params;
+        let idx = NttRlwe::flatten(indices_digest);
+        let mut found_buf = vec![0usize; rp.pertinent_count.max(1) * 4 + 64];
+        let mut found = 0usize;
+        check(unsafe {
+            omr_retrieve_indices(self.secret.raw, idx.as_ptr(), indices_digest.len() as u32, rp.all_payloads_count,
+                                 rp.pertinent_count, found_buf.as_mut_ptr(), found_buf.len(), &mut found)
+        })?;
+        found_buf.truncate(found.min(found_buf.len()));
+        let pay = NttRlwe::flatten(payloads_digest);
+        let mut out = vec![0u16; found_buf.len() * OMR_PAYLOAD_LEN];
+        check(unsafe {
+            omr_retrieve_payloads_seek(self.secret.raw, pay.as_ptr(), payloads_digest.len() as u32,
+                                       rp.all_payloads_count, rp.layout.combination_count, seed.as_ptr(),
+                                       seek.map_or(std::ptr::null(), |s| s as *const OmrWeightSeek),
+                                       found_buf.as_ptr(), found_buf.len(), out.as_mut_ptr())
         })?;
         let payloads = out
             .chunks_exact(OMR_PAYLOAD_LEN)

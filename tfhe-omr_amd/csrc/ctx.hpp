@@ -221,6 +221,12 @@ omr_status encode_payloads(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_p
 omr_status encode_payloads_indexed(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D,
                                    size_t offset, const WeightKey &key, uint32_t combos, uint32_t first_ct,
                                    uint32_t n_ct, uint32_t per_ct, uint64_t *d_out, hipStream_t st, bool accumulate);
+// The body of omr_encode_payloads_seek_device: as encode_payloads_indexed, the reference's weights found
+// through the seek (common.hpp, "Reference payload weights by seek"), which covers combos * all draws.
+omr_status encode_payloads_seek(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D, size_t offset,
+                                size_t all, const WeightKey &key, const omr_weight_seek &seek, uint32_t combos,
+                                uint32_t first_ct, uint32_t n_ct, uint32_t per_ct, uint64_t *d_out, hipStream_t st,
+                                bool accumulate);
 // The body of omr_encode_bitmap_device after its argument checks (bitmap_kernel.hpp): d_out is the whole
 // board's [omr_bitmap_ct_count(all)][2][N2]. accumulate = false: the touched ciphertexts are the sums of
 // their partials and the others zero; accumulate = true: the touched ones are added into, the others

@@ -1,7 +1,8 @@
 // Encode (detector.rs:223-453): the index and payload encode kernels' launches over the context's
 // partial-sum scratch, their reduction or accumulation, and the four encode entry points; the bitmap
 // digest's kernel (bitmap_kernel.hpp, none in the reference) the same way, with its two entry points;
-// the payload encode with indexed weights (none in the reference) and the device table of those weights.
+// the payload encode with indexed weights (none in the reference) and the device table of those weights;
+// the payload encode with the reference's weights by seek and the device builder of a seek.
 #include <algorithm>
 
 #include "bitmap_kernel.hpp"
@@ -84,6 +85,16 @@ omr_status omr::encode_payloads_indexed(omr_ctx *c, const uint64_t *pv, const ui
   return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
     encode_payloads_indexed_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, key, combos, first_ct,
                                                            (int)per_ct, per_wg, c->tab.tb.tw2, c->scr.partial);
+  });
+}
+
+omr_status omr::encode_payloads_seek(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, size_t offset,
+                                     size_t all, const WeightKey &key, const omr_weight_seek &seek, uint32_t combos,
+                                     uint32_t first_ct, uint32_t n_ct, uint32_t per_ct, uint64_t *out, hipStream_t st,
+                                     bool accumulate) {
+  return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
+    encode_payloads_seek_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, key, seek, combos, first_ct,
+                                                        (int)per_ct, per_wg, c->tab.tb.tw2, c->scr.partial);
   });
 }
 
@@ -233,6 +244,74 @@ extern "C" omr_status omr_indexed_weights_table_device(const uint8_t seed[32], s
       weight_key(seed), all, combos, (uint32_t)rows, d_out);
   HIP_TRY(hipGetLastError());
   return OMR_OK;
+}
+
+extern "C" omr_status omr_encode_payloads_seek_device(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
+                                                      size_t D, size_t offset, size_t all, const uint8_t seed[32],
+                                                      const omr_weight_seek *seek, uint32_t combos, uint32_t first_ct,
+                                                      uint32_t n_ct, uint32_t per_ct, uint64_t *out, void *stream) {
+  if (!c || !out || !seed || !seek || (D && (!pv || !payloads)) || n_ct == 0 || per_ct == 0 ||
+      per_ct * PAYLOAD_LEN > (uint32_t)N2 || offset > all || D > all - offset || D > (size_t)INT32_MAX ||
+      n_ct > 65535)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_seek_device: bad argument");
+  if (!seek_covers(seek, combos, all))
+    return set_error(OMR_ERR_INVALID_ARGUMENT,
+                     "omr_encode_payloads_seek_device: the seek does not cover combination_count * all draws");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // NULL: HIP's null stream
+  return encode_payloads_seek(c, pv, payloads, D, offset, all, weight_key(seed), *seek, combos, first_ct, n_ct, per_ct,
+                              out, (hipStream_t)stream, false);
+}
+
+extern "C" omr_status omr_encode_payloads_seek(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                               size_t offset, size_t all, const uint8_t seed[32],
+                                               const omr_weight_seek *seek, uint32_t combos, uint32_t first_ct,
+                                               uint32_t n_ct, uint32_t per_ct, uint64_t *out) {
+  if (!c || !out || !seed || !seek || (D && (!pv || !payloads)) || n_ct == 0)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_seek");
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<uint64_t> dpv, dout;
+  DevBuf<uint16_t> dpay;
+  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
+  HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
+  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
+  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
+  OMR_TRY(omr_encode_payloads_seek_device(c, dpv, dpay, D, offset, all, seed, seek, combos, first_ct, n_ct, per_ct, dout,
+                                          c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+
+// The device builder of a seek: weight_seek_scan_kernel over the raw words [0, draws + OMR_WEIGHT_SEEK_MAX] on
+// the current device, then the few hits sorted and turned into at[] on the host (common.hpp, seek_from_hits).
+extern "C" omr_status omr_weight_seek_build_zone_device(const uint8_t seed[32], uint64_t draws, uint32_t zone,
+                                                        omr_weight_seek *out, void *stream) {
+  const char *who = "omr_weight_seek_build_device";
+  if (!seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  if (draws >= SEEK_MAX_DRAWS) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": draws beyond 2^62");
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t last = draws + OMR_WEIGHT_SEEK_MAX, nblk = (last >> 4) + 1;
+  constexpr uint64_t MAX_GRID = 256 * 8;  // 8 workgroups of 256 threads per CU: the rest is the grid-stride loop
+  const unsigned grid = (unsigned)std::min<uint64_t>((nblk + SEEK_SCAN_T - 1) / SEEK_SCAN_T, MAX_GRID);
+  DevBuf<unsigned long long> d_hits;  // the count, then SEEK_LIST slots
+  unsigned long long hits[1 + SEEK_LIST] = {};
+  HIP_TRY(d_hits.alloc(1 + SEEK_LIST));
+  HIP_TRY(hipMemsetAsync(d_hits, 0, sizeof hits, st));
+  weight_seek_scan_kernel<<<grid, SEEK_SCAN_T, 0, st>>>(weight_key(seed), nblk, last, zone, d_hits);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hits, d_hits, sizeof hits, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t list[SEEK_LIST];
+  std::copy(hits + 1, hits + 1 + SEEK_LIST, list);
+  return seek_from_hits(list, hits[0], draws, zone, out, who);
+}
+
+extern "C" omr_status omr_weight_seek_build_device(const uint8_t seed[32], uint64_t draws, omr_weight_seek *out,
+                                                   void *stream) {
+  return omr_weight_seek_build_zone_device(seed, draws, OMR_WEIGHT_ZONE, out, stream);
 }
 
 extern "C" omr_status omr_encode_bitmap_device(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset, size_t all,

@@ -240,6 +240,126 @@ __global__ void indexed_weights_table_kernel(WeightKey key, uint64_t all, uint32
   for (int i = 0; i < 16 && g0 + i < all; ++i) o[i] = w[i];
 }
 
+// encode_payloads_indexed_kernel with the reference's weights found through a seek (common.hpp,
+// "Reference payload weights by seek"): the same grid, accumulation and partials, the same bits as
+// encode_payloads_kernel over omr_payload_weights' table. Row j of the board starts at draw j * all, so the
+// staged messages g0 .. g0 + cnt - 1 of combination j are the draws n0 = j * all + g0 onward, at the raw
+// positions pos(n0) .. pos(n0 + cnt - 1) <= pos(n0) + cnt - 1 + OMR_WEIGHT_SEEK_MAX: with the first one
+// anywhere in its block, at most ENC_SEEK_WORDS raw words in ENC_SEEK_BLOCKS ChaCha blocks from block
+// pos(n0) >> 4. Thread t < per_ct * ENC_SEEK_BLOCKS computes block t % ENC_SEEK_BLOCKS of combination
+// t / ENC_SEEK_BLOCKS and writes each accepted word to the place of its draw, wts[j][draw - n0]: the LDS
+// holds the staged messages' weights in message order (rejected words dropped), and the accumulation
+// loop is the indexed kernel's.
+constexpr int ENC_SEEK_WORDS = ENC_T + 15 + OMR_WEIGHT_SEEK_MAX;  // 175: the most raw words one staged row spans
+constexpr int ENC_SEEK_BLOCKS = (ENC_SEEK_WORDS + 15) / 16;       // 11
+static_assert(ENC_SEEK_BLOCKS * 16 >= ENC_SEEK_WORDS, "the staged blocks cover the raw span of a row");
+static_assert(ENC_W_PER_CT * ENC_SEEK_BLOCKS <= ENC_T, "one thread per staged raw block");
+__global__ __launch_bounds__(ENC_T) void encode_payloads_seek_kernel(
+    const uint64_t *__restrict__ pv, const uint16_t *__restrict__ payloads, int D, uint64_t offset, uint64_t all,
+    WeightKey key, omr_weight_seek seek, uint32_t combos, uint32_t first_ct, int per_ct, int per_wg,
+    const double *__restrict__ tw, uint64_t *__restrict__ partial) {
+  using M = Mod<2>;
+  constexpr int T = ENC_T, E = ENC_E, N = N2;
+  using NTT = WgNtt<M, T, E>;
+  __shared__ double xch[NTT::LDS_DOUBLES];
+  __shared__ uint16_t wts[ENC_W_PER_CT][ENC_T];
+  const int tid = threadIdx.x;
+  const int chunk = blockIdx.x, c = blockIdx.y;
+  const int m0 = chunk * per_wg;
+  const int mcount = min(per_wg, D - m0);
+  const uint64_t combo0 = ((uint64_t)first_ct + (uint64_t)c) * (uint64_t)per_ct;
+  double accA[E], accB[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) accA[e] = accB[e] = 0.0;
+  // per_wg may exceed ENC_T (large D): the weights are staged ENC_T messages at a time
+#pragma unroll 1
+  for (int mb = 0; mb < mcount; mb += ENC_T) {
+    const int cnt = min(ENC_T, mcount - mb);
+    const uint64_t g0 = offset + m0 + mb;
+    __syncthreads();  // every thread has finished reading the previous block's weights
+    if (tid < per_ct * ENC_SEEK_BLOCKS) {
+      const int j = tid / ENC_SEEK_BLOCKS, b = tid - j * ENC_SEEK_BLOCKS;
+      if (combo0 + j < (uint64_t)combos) {
+        const uint64_t n0 = (combo0 + j) * all + g0;  // the row's first staged draw
+        const uint64_t blk = (seek_pos(seek, n0) >> 4) + b;
+        if (blk <= seek_pos(seek, n0 + cnt - 1) >> 4) {
+          uint32_t w[16];
+          chacha_block(12, key.k, blk, 0, w);
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            uint64_t draw;
+            const bool accepted = seek_draw_at(seek, blk * 16 + i, &draw);
+            const uint64_t at = draw - n0;  // wraps to a large value for a draw before n0
+            if (accepted && at < (uint64_t)cnt) wts[j][at] = weight_of_word(w[i]);
+          }
+        }
+      } else {
+        for (int i = b; i < cnt; i += ENC_SEEK_BLOCKS) wts[j][i] = 0;
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int mi = mb; mi < mb + cnt; ++mi) {
+      const int m = m0 + mi;
+      const int wi = mi - mb;
+      double x[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int pos = tid + e * T;
+        const int j = pos / PAYLOAD_LEN;
+        double v = 0.0;
+        if (j < per_ct) {
+          const int l = pos - j * PAYLOAD_LEN;
+          const uint32_t w = wts[j][wi];
+          v = centred_lift(((uint32_t)payloads[(size_t)m * PAYLOAD_LEN + l] * w) % (uint32_t)P);
+        }
+        x[e] = v;
+      }
+      NTT::fwd(x, xch, tw, tid);
+      const uint64_t *pa = pv + (size_t)m * 2 * N + tid * E;
+      const uint64_t *pb = pa + N;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        accA[e] = red<M>(accA[e] + mm<M>(from_u64<M>(pa[e]), x[e]));
+        accB[e] = red<M>(accB[e] + mm<M>(from_u64<M>(pb[e]), x[e]));
+      }
+    }
+  }
+  uint64_t *o = partial + ((size_t)c * gridDim.x + chunk) * 2 * N + tid * E;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    o[e] = to_u64<M>(canon<M>(accA[e]));
+    o[N + e] = to_u64<M>(canon<M>(accB[e]));
+  }
+}
+
+// The builders' scan (omr_weight_seek_build_device): one ChaCha12 block of the reference stream per thread
+// and grid-stride step, its 16 words compared with the zone. A rejected word at a raw position <= last takes
+// a slot of the list with one atomic; only the first SEEK_LIST slots exist, and the count says whether
+// the list is complete (common.hpp, SEEK_LIST). hits[0] is the count, hits[1 ..] the list.
+constexpr int SEEK_SCAN_T = 256;
+__global__ __launch_bounds__(SEEK_SCAN_T) void weight_seek_scan_kernel(WeightKey key, uint64_t nblk, uint64_t last,
+                                                                      uint32_t zone,
+                                                                      unsigned long long *__restrict__ hits) {
+  const uint64_t stride = (uint64_t)gridDim.x * SEEK_SCAN_T;
+  for (uint64_t b = (uint64_t)blockIdx.x * SEEK_SCAN_T + threadIdx.x; b < nblk; b += stride) {
+    uint32_t w[16];
+    chacha_block(12, key.k, b, 0, w);
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) any = any || weight_rejected(w[i], zone);
+    if (!any) continue;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const uint64_t r = b * 16 + i;
+      if (weight_rejected(w[i], zone) && r <= last) {
+        const unsigned long long slot = atomicAdd(&hits[0], 1ull);
+        if (slot < SEEK_LIST) hits[1 + slot] = r;
+      }
+    }
+  }
+}
+
 // out[c][t] = sum_chunk partial[c][chunk][t] mod q2: every partial is canonical (< q2), so the
 // running sum stays canonical with one conditional subtraction per term, for any chunk count.
 __global__ void reduce_partials_kernel(const uint64_t *__restrict__ partial, int chunks,

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -407,6 +408,72 @@ extern "C" omr_status omr_indexed_weights_table(const uint8_t seed[32], size_t a
     for (size_t b = b0; b < b1; ++b) {
       indexed_weight_block(key, (uint32_t)j, b, w);
       for (size_t i = 0; i < 16 && b * 16 + i < all; ++i) o[b * 16 + i] = w[i];
+    }
+  });
+  return OMR_OK;
+}
+
+// Reference payload weights by seek (include/omr_gpu.h), host side: the scan that finds the stream's
+// rejections and the recipient's matrix, over common.hpp's statement.
+extern "C" omr_status omr_weight_seek_build_zone_cpu(const uint8_t seed[32], uint64_t draws, uint32_t zone,
+                                                     int nthreads, omr_weight_seek *out) {
+  const char *who = "omr_weight_seek_build_cpu";
+  if (!seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  if (draws >= SEEK_MAX_DRAWS) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": draws beyond 2^62");
+  const WeightKey key = weight_key(seed);
+  const uint64_t last = draws + OMR_WEIGHT_SEEK_MAX;  // the last raw word scanned
+  constexpr uint64_t PIECE = 4096;                    // ChaCha blocks per work item
+  const uint64_t nblk = (last >> 4) + 1, pieces = (nblk + PIECE - 1) / PIECE;
+  std::vector<uint64_t> hits;  // every piece's first SEEK_LIST rejections: the stream's first SEEK_LIST are among them
+  std::mutex mu;
+  parallel_for((size_t)pieces, nthreads, [&](size_t it) {
+    uint64_t mine[SEEK_LIST];
+    uint32_t n = 0;
+    const uint64_t b1 = std::min(nblk, ((uint64_t)it + 1) * PIECE);
+    for (uint64_t b = (uint64_t)it * PIECE; b < b1 && n < SEEK_LIST; ++b) {
+      uint32_t w[16];
+      chacha_block(12, key.k, b, 0, w);
+      for (int i = 0; i < 16 && n < SEEK_LIST; ++i)
+        if (weight_rejected(w[i], zone) && b * 16 + i <= last) mine[n++] = b * 16 + i;
+    }
+    if (n) {
+      std::lock_guard<std::mutex> lk(mu);
+      hits.insert(hits.end(), mine, mine + n);
+    }
+  });
+  std::sort(hits.begin(), hits.end());
+  // more than SEEK_LIST found: the smallest SEEK_LIST + 1 decide, and seek_from_hits reports the overflow
+  return seek_from_hits(hits.data(), std::min<uint64_t>(hits.size(), SEEK_LIST + 1), draws, zone, out, who);
+}
+
+extern "C" omr_status omr_weight_seek_build_cpu(const uint8_t seed[32], uint64_t draws, int nthreads,
+                                                omr_weight_seek *out) {
+  return omr_weight_seek_build_zone_cpu(seed, draws, OMR_WEIGHT_ZONE, nthreads, out);
+}
+
+extern "C" omr_status omr_payload_weights_at(const uint8_t seed[32], size_t all, uint32_t combos,
+                                             const omr_weight_seek *seek, uint32_t first_combo, uint32_t n_combos,
+                                             const size_t *indices, size_t n_indices, uint16_t *out, int nthreads) {
+  if (!seed || !seek || (n_indices && !indices) || (n_combos && n_indices && !out))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_payload_weights_at: NULL argument");
+  if (!seek_covers(seek, combos, all))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_payload_weights_at: the seek does not cover combination_count * all draws");
+  for (size_t k = 0; k < n_indices; ++k)
+    if (indices[k] >= all) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_payload_weights_at: index out of range");
+  const WeightKey key = weight_key(seed);
+  parallel_for(n_combos, nthreads, [&](size_t r) {
+    uint16_t *o = out + r * n_indices;
+    const uint64_t j = (uint64_t)first_combo + r;
+    if (j >= combos) {  // a padding combination
+      std::fill(o, o + n_indices, (uint16_t)0);
+      return;
+    }
+    uint32_t w[16];
+    uint64_t have = 0;  // the block in w, valid once k > 0: sorted indices share blocks
+    for (size_t k = 0; k < n_indices; ++k) {
+      const uint64_t p = seek_pos(*seek, j * (uint64_t)all + indices[k]);
+      if (k == 0 || (p >> 4) != have) chacha_block(12, key.k, have = p >> 4, 0, w);
+      o[k] = weight_of_word(w[p & 15]);
     }
   });
   return OMR_OK;

@@ -1,7 +1,7 @@
 // Retrieval on the auditor (include/omr_gpu.h, "Solve mod 257"): the device solver of solve_kernels.hpp and
 // the device twins of omr_retrieve_indices / omr_retrieve_payloads[_indexed] (retriever.hip). The decode is
 // audit_kernel through audit.hip's audit_decode_to_device; the index buckets are read on the host from the
-// decoded values copied back; the indexed matrix and the right-hand side are built on the device, the
+// decoded values copied back; the indexed or seek matrix and the right-hand side are built on the device, the
 // solver runs there, and the solution and its status word are copied back.
 #include <algorithm>
 #include <set>
@@ -189,11 +189,21 @@ omr_status indices_locked(omr_auditor *aud, const void *idx_cts, uint32_t n_ct, 
   return OMR_OK;
 }
 
-// retrieve_payloads_body's device twin after the NULL checks: weights (table) or weight_seed (indexed).
+// Where the system's matrix comes from: the table's entries, the indexed weights of a seed, or the
+// reference's weights of a seed through a seek (seek NULL: built here, on the auditor's device).
+struct MatrixSource {
+  const uint16_t *weights = nullptr;
+  const uint8_t *weight_seed = nullptr;
+  bool by_seek = false;
+  const omr_weight_seek *seek = nullptr;
+};
+
+// retrieve_payloads_body's device twin after the NULL checks.
 omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits, size_t all,
-                           uint32_t combination_count, const uint16_t *weights, const uint8_t *weight_seed,
-                           const size_t *indices, size_t n_indices, uint16_t *payloads, omr_audit_summary *summary,
-                           const std::string &who) {
+                           uint32_t combination_count, const MatrixSource &src, const size_t *indices,
+                           size_t n_indices, uint16_t *payloads, omr_audit_summary *summary, const std::string &who) {
+  const uint16_t *weights = src.weights;
+  const uint8_t *weight_seed = src.weight_seed;
   omr_retrieval_params rp;
   OMR_TRY(omr_get_retrieval_params(all, n_indices, &rp));
   const size_t rows = combination_count ? combination_count : rp.combination_count, cols = n_indices,
@@ -207,6 +217,17 @@ omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": more than OMR_SOLVE_MAX_ROWS (8192) combinations");
   omr_auditor::Retrieve &r = aud->ret;
   hipStream_t st = aud->st;
+  omr_weight_seek seek{};
+  if (src.by_seek) {
+    if (src.seek) {
+      if (!seek_covers(src.seek, rows, all))
+        return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": the seek does not cover combination_count * all draws");
+      seek = *src.seek;
+    } else {
+      if (all > SEEK_MAX_DRAWS / (rows + 1)) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": board too large");
+      OMR_TRY(omr_weight_seek_build_device(weight_seed, (uint64_t)rows * all, &seek, st));
+    }
+  }
   OMR_TRY(decode_cts(aud, pay_cts, n_ct, bits, summary, who.c_str()));
   // the stream is idle here (the decode ends with a synchronisation), so growing is safe
   HIP_TRY(r.matrix.reserve(rows * cols));
@@ -224,8 +245,12 @@ omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
     h_idx.assign(indices, indices + cols);
     HIP_TRY(r.indices.reserve(cols));
     HIP_TRY(hipMemcpyAsync(r.indices, h_idx.data(), cols * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    retrieve_matrix_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(weight_key(weight_seed), r.indices, (uint32_t)rows,
-                                                                          (uint32_t)cols, r.matrix);
+    if (src.by_seek)
+      retrieve_matrix_seek_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(weight_key(weight_seed), seek, all, r.indices,
+                                                                                 (uint32_t)rows, (uint32_t)cols, r.matrix);
+    else
+      retrieve_matrix_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(weight_key(weight_seed), r.indices, (uint32_t)rows,
+                                                                            (uint32_t)cols, r.matrix);
   }
   retrieve_rhs_kernel<<<col_grid(rows * PAYLOAD_LEN), SOLVE_COL_T, 0, st>>>(r.decoded, (uint32_t)rows, (uint32_t)per, r.rhs);
   omr_status s = hipGetLastError() == hipSuccess ? OMR_OK : set_error(OMR_ERR_DEVICE, who + ": kernel launch failed");
@@ -277,7 +302,7 @@ extern "C" omr_status omr_auditor_retrieve_payloads(omr_auditor *aud, const void
   OMR_TRY(check_bits(bits, who));
   std::lock_guard<std::mutex> lk(aud->mu);
   HIP_TRY(hipSetDevice(aud->device));
-  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, weights, nullptr, indices,
+  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, MatrixSource{weights}, indices,
                          n_indices, payloads, nullptr, who);
 }
 
@@ -291,8 +316,22 @@ extern "C" omr_status omr_auditor_retrieve_payloads_indexed(omr_auditor *aud, co
   OMR_TRY(check_bits(bits, who));
   std::lock_guard<std::mutex> lk(aud->mu);
   HIP_TRY(hipSetDevice(aud->device));
-  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, nullptr, weight_seed, indices,
-                         n_indices, payloads, nullptr, who);
+  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, MatrixSource{nullptr, weight_seed},
+                         indices, n_indices, payloads, nullptr, who);
+}
+
+extern "C" omr_status omr_auditor_retrieve_payloads_seek(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
+                                                         size_t all_payloads_count, uint32_t combination_count,
+                                                         const uint8_t weight_seed[32], const omr_weight_seek *seek,
+                                                         const size_t *indices, size_t n_indices, uint16_t *payloads) {
+  const std::string who = "omr_auditor_retrieve_payloads_seek";
+  if (!aud || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
+  OMR_TRY(check_bits(bits, who));
+  std::lock_guard<std::mutex> lk(aud->mu);
+  HIP_TRY(hipSetDevice(aud->device));
+  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count,
+                         MatrixSource{nullptr, weight_seed, true, seek}, indices, n_indices, payloads, nullptr, who);
 }
 
 extern "C" omr_status omr_auditor_decode_digest_indexed(omr_auditor *aud, const void *idx_cts, uint32_t n_idx_ct,
@@ -312,8 +351,8 @@ extern "C" omr_status omr_auditor_decode_digest_indexed(omr_auditor *aud, const 
   OMR_TRY(indices_locked(aud, idx_cts, n_idx_ct, bits, rp, pertinent_count, indices, cap, found, summary ? &sum : nullptr,
                          who.c_str()));
   if (cap < *found) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": more indices found than cap");
-  OMR_TRY(payloads_locked(aud, pay_cts, n_pay_ct, bits, all_payloads_count, rp.combination_count, nullptr, weight_seed,
-                          indices, *found, payloads, summary ? &sum : nullptr, who));
+  OMR_TRY(payloads_locked(aud, pay_cts, n_pay_ct, bits, all_payloads_count, rp.combination_count,
+                          MatrixSource{nullptr, weight_seed}, indices, *found, payloads, summary ? &sum : nullptr, who));
   if (summary) merge_summary(*summary, sum);
   return OMR_OK;
 }

@@ -264,6 +264,28 @@ extern "C" omr_status omr_solve_mod257_cpu(const uint16_t *matrix, const uint16_
   }
 }
 
+extern "C" omr_status omr_retrieve_payloads_seek(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
+                                                 size_t all_payloads_count, uint32_t combination_count,
+                                                 const uint8_t weight_seed[32], const omr_weight_seek *seek,
+                                                 const size_t *indices, size_t n_indices, uint16_t *payloads) {
+  if (!sk || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_seek: NULL argument");
+  return retrieve_payloads_body(
+      sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
+      "omr_retrieve_payloads_seek", [&](size_t rows, uint16_t *m) {
+        // every row is a real combination of the board: rows = combination_count (or its default)
+        omr_weight_seek built;
+        if (!seek) {
+          if (all_payloads_count > SEEK_MAX_DRAWS / (rows + 1))
+            return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_seek: board too large");
+          const omr_status b = omr_weight_seek_build_cpu(weight_seed, (uint64_t)rows * all_payloads_count, 0, &built);
+          if (b != OMR_OK) return b;
+        }
+        return omr_payload_weights_at(weight_seed, all_payloads_count, (uint32_t)rows, seek ? seek : &built, 0,
+                                      (uint32_t)rows, indices, n_indices, m, 0);
+      });
+}
+
 extern "C" omr_status omr_bitmap_ct_count(size_t all, uint32_t *n_ct) {
   if (!n_ct) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_bitmap_ct_count: NULL argument");
   const size_t n = all / OMR_BITMAP_MESSAGES_PER_CT + (all % OMR_BITMAP_MESSAGES_PER_CT != 0);

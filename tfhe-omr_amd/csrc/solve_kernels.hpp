@@ -297,6 +297,22 @@ retrieve_matrix_kernel(WeightKey key, const uint64_t *__restrict__ indices, uint
   m[idx] = v;
 }
 
+// The same matrix in the reference's convention (common.hpp, "Reference payload weights by seek"):
+// m[j][k] = w(j * all + indices[k]), the word at raw position pos(n) of the reference stream.
+__global__ void __launch_bounds__(SOLVE_COL_T)
+retrieve_matrix_seek_kernel(WeightKey key, omr_weight_seek seek, uint64_t all, const uint64_t *__restrict__ indices,
+                            uint32_t rows, uint32_t cols, uint16_t *__restrict__ m) {
+  const size_t idx = (size_t)blockIdx.x * SOLVE_COL_T + threadIdx.x;
+  if (idx >= (size_t)rows * cols) return;
+  const uint64_t p = seek_pos(seek, (uint64_t)(idx / cols) * all + indices[idx % cols]);
+  uint32_t w[16];
+  chacha_block(12, key.k, p >> 4, 0, w);
+  uint32_t v = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) v = (p & 15) == (uint64_t)i ? w[i] : v;  // no runtime-indexed local array
+  m[idx] = weight_of_word(v);
+}
+
 // The right-hand side of a retrieval from decoded payload ciphertexts u16 [n_ct][2048]: combination j is in
 // ciphertext j / per, slots (j % per) * 612 onward.
 __global__ void __launch_bounds__(SOLVE_COL_T)

@@ -5,7 +5,8 @@
 // indices and their payloads come back.
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
-//           [--compact BITS] [--audit-key] [--indexed-weights] [--device-retrieve] [--host-only]
+//           [--compact BITS] [--audit-key] [--indexed-weights] [--seek-weights] [--device-retrieve]
+//           [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -36,6 +37,11 @@
 // the detector encodes with omr_encode_payloads_indexed (or a session from omr_digest_begin_indexed) and the
 // recipient solves with omr_retrieve_payloads_indexed; nobody draws the board-wide weight table. With
 // --host-only it checks omr_indexed_weights_at against omr_indexed_weights_table on the pertinent set.
+// --seek-weights keeps the reference's weights and drops the table (include/omr_gpu.h, "Reference payload weights
+// by seek"): the detector builds the seek of the board on its device and encodes with omr_encode_payloads_seek
+// (or a session from omr_digest_begin_seek), the recipient solves with omr_retrieve_payloads_seek, which builds its
+// own seek (with --device-retrieve: omr_auditor_retrieve_payloads_seek, on the auditor's device). With --host-only
+// it checks omr_payload_weights_at against omr_payload_weights' table on the pertinent set.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -77,7 +83,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false, device_retrieve = false;
+  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false, seek_weights = false, device_retrieve = false;
   int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -91,11 +97,13 @@ int main(int argc, char **argv) {
     else if (a == "--compact" && i + 1 < argc) compact_bits = std::atoi(argv[++i]);
     else if (a == "--audit-key") audit_key = true;
     else if (a == "--indexed-weights") indexed = true;
+    else if (a == "--seek-weights") seek_weights = true;
     else if (a == "--device-retrieve") device_retrieve = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--device-retrieve] [--host-only]\n",
+                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--seek-weights] "
+                   "[--device-retrieve] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -174,9 +182,14 @@ int main(int argc, char **argv) {
   CHECK(omr_get_retrieval_params(D, pert_count, &rp));
   uint8_t wseed[32];
   for (int i = 0; i < 32; ++i) wseed[i] = (uint8_t)(rng() & 0xff);
-  // the board-wide table of the reference's weights; with --indexed-weights nobody needs one
-  std::vector<uint16_t> weights(indexed ? 0 : (size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * D);
-  if (!indexed)
+  if (indexed && seek_weights) {
+    std::fprintf(stderr, "--indexed-weights and --seek-weights are two conventions: choose one\n");
+    return 2;
+  }
+  // the board-wide table of the reference's weights; with --indexed-weights or --seek-weights nobody needs one
+  const bool table = !indexed && !seek_weights;
+  std::vector<uint16_t> weights(table ? (size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * D : 0);
+  if (table)
     CHECK(omr_payload_weights(wseed, D, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
                               weights.data()));
   std::printf("retrieval params: %u index ct, %u payload ct (%u combinations)\n",
@@ -217,6 +230,25 @@ int main(int argc, char **argv) {
       return 1;
     }
     std::printf("host-only: indexed weights OK (%zu x %zu submatrix of a %zu x %zu table)\n", rows, pert_count, rows, D);
+  }
+  if (host_only && seek_weights) {
+    // the recipient's submatrix through the seek against the table the reference would draw
+    const size_t rows = (size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher;
+    std::vector<uint16_t> tab(rows * D), at(rows * pert_count);
+    omr_weight_seek sk;
+    CHECK(omr_payload_weights(wseed, D, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher, tab.data()));
+    CHECK(omr_weight_seek_build_cpu(wseed, (uint64_t)rp.combination_count * D, 0, &sk));
+    CHECK(omr_payload_weights_at(wseed, D, rp.combination_count, &sk, 0, (uint32_t)rows, pert.data(), pert_count,
+                                 at.data(), 0));
+    bool ok = true;
+    for (size_t j = 0; j < rows; ++j)
+      for (size_t k = 0; k < pert_count; ++k) ok = ok && at[j * pert_count + k] == tab[j * D + pert[k]];
+    if (!ok) {
+      std::printf("Fail: omr_payload_weights_at differs from omr_payload_weights\nFAILED\n");
+      return 1;
+    }
+    std::printf("host-only: seek weights OK (%zu x %zu submatrix of a %zu x %zu table, %u rejections)\n", rows, pert_count,
+                rows, D, sk.n);
   }
   if (host_only) {
     std::printf("host-only: keys, clues, weights and parameters OK\n");
@@ -280,6 +312,7 @@ int main(int argc, char **argv) {
     t = clk::now();
     omr_digest *dg = nullptr;
     if (indexed) CHECK(omr_digest_begin_indexed(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
+    else if (seek_weights) CHECK(omr_digest_begin_seek(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
     else CHECK(omr_digest_begin(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
     if (bitmap) CHECK(omr_digest_enable_bitmap(dg));
     for (size_t off = 0; off < D; off += session_piece) {
@@ -327,13 +360,21 @@ int main(int argc, char **argv) {
       CHECK(omr_encode_indices(ctx, pv.data(), D, 0, D, seed + 3, c, &idx_ct[(size_t)c * 2 * N2]));
     std::printf("encode indices time: %.3f s\n", secs(t));
     t = clk::now();
-    if (indexed)
+    if (indexed) {
       CHECK(omr_encode_payloads_indexed(ctx, pv.data(), payloads.data(), D, 0, D, wseed, rp.combination_count, 0, n_pay,
                                         rp.cmb_count_per_cipher, pay_ct.data()));
-    else
+    } else if (seek_weights) {
+      // the scan runs on the calling thread's current HIP device: the detector's, selected when it was created
+      omr_weight_seek sk;
+      CHECK(omr_weight_seek_build_device(wseed, (uint64_t)rp.combination_count * D, &sk, nullptr));
+      std::printf("weight seek: %u rejections in %llu draws\n", sk.n, (unsigned long long)sk.draws);
+      CHECK(omr_encode_payloads_seek(ctx, pv.data(), payloads.data(), D, 0, D, wseed, &sk, rp.combination_count, 0, n_pay,
+                                     rp.cmb_count_per_cipher, pay_ct.data()));
+    } else
       CHECK(omr_encode_payloads(ctx, pv.data(), payloads.data(), D, 0, D, weights.data(), n_pay,
                                 rp.cmb_count_per_cipher, pay_ct.data()));
-    std::printf("encode pertinent payloads time: %.3f s%s\n", secs(t), indexed ? " (indexed weights)" : "");
+    std::printf("encode pertinent payloads time: %.3f s%s\n", secs(t),
+                indexed ? " (indexed weights)" : seek_weights ? " (reference weights by seek)" : "");
     if (bitmap) {
       t = clk::now();
       CHECK(omr_encode_bitmap(ctx, pv.data(), D, 0, D, bmp_ct.data()));
@@ -421,12 +462,18 @@ int main(int argc, char **argv) {
   if (device_retrieve && indexed)
     CHECK(omr_auditor_retrieve_payloads_indexed(ra, dev_pay, n_pay, compact_bits, D, rp.combination_count, wseed,
                                                 found.data(), found.size(), solved.data()));
+  else if (device_retrieve && seek_weights)
+    CHECK(omr_auditor_retrieve_payloads_seek(ra, dev_pay, n_pay, compact_bits, D, rp.combination_count, wseed, nullptr,
+                                             found.data(), found.size(), solved.data()));
   else if (device_retrieve)
     CHECK(omr_auditor_retrieve_payloads(ra, dev_pay, n_pay, compact_bits, D, rp.combination_count, weights.data(),
                                         found.data(), found.size(), solved.data()));
   else if (indexed)
     CHECK(omr_retrieve_payloads_indexed(pa, pay_ct.data(), n_pay, D, rp.combination_count, wseed, found.data(),
                                         found.size(), solved.data()));
+  else if (seek_weights)
+    CHECK(omr_retrieve_payloads_seek(pa, pay_ct.data(), n_pay, D, rp.combination_count, wseed, nullptr, found.data(),
+                                     found.size(), solved.data()));
   else
     CHECK(omr_retrieve_payloads(pa, pay_ct.data(), n_pay, D, rp.combination_count, weights.data(), found.data(),
                                 found.size(), solved.data()));

@@ -251,6 +251,26 @@ EXPORTS = {
     "omr_auditor_decode_digest_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
                                                     C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                                     C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]),
+    # reference payload weights by seek (include/omr_gpu.h); the omr_weight_seek pointers are void *
+    "omr_weight_seek_build_cpu": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "omr_weight_seek_build_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "omr_weight_seek_build_zone_cpu": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p]),
+    "omr_weight_seek_build_zone_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "omr_payload_weights_at": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    "omr_encode_payloads_seek": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_void_p]),
+    "omr_encode_payloads_seek_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "omr_digest_begin_seek": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]),
+    "omr_retrieve_payloads_seek": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "omr_auditor_retrieve_payloads_seek": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_size_t,
+                                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p]),
 }
 
 _lib = None
@@ -349,6 +369,78 @@ def indexed_weights_table_device(seed: bytes, all_payloads_count: int, combinati
     ptr, _keep = _seed_ptr(seed)
     _check(lib().omr_indexed_weights_table_device(ptr, all_payloads_count, combination_count, n_ct, per_ct,
                                                   d_out or None, stream or None), "omr_indexed_weights_table_device")
+
+
+WEIGHT_SEEK_MAX = 32
+WEIGHT_ZONE = 0xFFFFFFFE
+
+
+class _WeightSeek(C.Structure):
+    _fields_ = [("draws", C.c_uint64), ("n", C.c_uint32), ("zone", C.c_uint32), ("at", C.c_uint64 * WEIGHT_SEEK_MAX)]
+
+
+class WeightSeek:
+    """omr_weight_seek (include/omr_gpu.h, "Reference payload weights by seek"): the rejections of
+    omr_payload_weights' stream that matter for its first `draws` accepted draws; `at[k] = r_k - k`."""
+
+    def __init__(self, draws: int = 0, at=(), zone: int = WEIGHT_ZONE, n: int = None):
+        self._t = _WeightSeek(draws, len(at) if n is None else n, zone)
+        for k, v in enumerate(at):
+            self._t.at[k] = v
+
+    draws = property(lambda self: self._t.draws)
+    n = property(lambda self: self._t.n)
+    zone = property(lambda self: self._t.zone)
+    at = property(lambda self: [int(self._t.at[k]) for k in range(min(self._t.n, WEIGHT_SEEK_MAX))])
+
+    @property
+    def ptr(self):
+        return C.addressof(self._t)
+
+    def __eq__(self, other):
+        return (self.draws, self.n, self.zone, self.at) == (other.draws, other.n, other.zone, other.at)
+
+    def __repr__(self):
+        return f"WeightSeek(draws={self.draws}, at={self.at}, zone={self.zone:#x})"
+
+    @classmethod
+    def build(cls, seed: bytes, draws: int, zone: int = None, device: bool = False, nthreads: int = 0,
+              stream: int = 0) -> "WeightSeek":
+        """omr_weight_seek_build_cpu / _device (zone given: the _zone_ stage entries): scan the stream of
+        `seed` for the rejections of its first `draws` draws, on the host or on the current HIP device."""
+        s = cls()
+        ptr, _keep = _seed_ptr(seed)
+        L = lib()
+        if device:
+            st = (L.omr_weight_seek_build_device(ptr, draws, s.ptr, stream or None) if zone is None else
+                  L.omr_weight_seek_build_zone_device(ptr, draws, zone, s.ptr, stream or None))
+        else:
+            st = (L.omr_weight_seek_build_cpu(ptr, draws, nthreads, s.ptr) if zone is None else
+                  L.omr_weight_seek_build_zone_cpu(ptr, draws, zone, nthreads, s.ptr))
+        _check(st, "omr_weight_seek_build_device" if device else "omr_weight_seek_build_cpu")
+        return s
+
+    @classmethod
+    def for_board(cls, seed: bytes, rp: "RetrievalParams", device: bool = False) -> "WeightSeek":
+        """The seek of a board: combination_count * all draws."""
+        return cls.build(seed, rp.combination_count * rp.all_payloads_count, device=device)
+
+
+def _seek_ptr(seek):
+    return None if seek is None else seek.ptr
+
+
+def payload_weights_at(seed: bytes, all_payloads_count: int, combination_count: int, seek: "WeightSeek", indices,
+                       first_combo: int = 0, n_combos: int = None, nthreads: int = 0) -> np.ndarray:
+    """omr_payload_weights_at: u16 [n_combos][len(indices)], omr_payload_weights' weight (first_combo + r,
+    indices[k]) found through the seek, no table; rows at or beyond combination_count are zero."""
+    idx = np.ascontiguousarray(indices, dtype=np.uintp).reshape(-1)
+    n = max(combination_count - first_combo, 0) if n_combos is None else n_combos
+    out = np.empty((n, idx.size), np.uint16)
+    ptr, _keep = _seed_ptr(seed)
+    _check(lib().omr_payload_weights_at(ptr, all_payloads_count, combination_count, _seek_ptr(seek), first_combo, n,
+                                        idx.ctypes.data, idx.size, out.ctypes.data, nthreads), "omr_payload_weights_at")
+    return out
 
 
 @dataclass
@@ -666,6 +758,21 @@ class Retriever:
         _check(lib().omr_retrieve_payloads_indexed(self._sk._h, cts.reshape(-1), cts.shape[0], rp.all_payloads_count,
                                                    rp.combination_count, ptr, idx, len(idx), out.reshape(-1)),
                "omr_retrieve_payloads_indexed")
+        return out
+
+    def decode_combined_payloads_and_solve_seek(self, pay_cts, seed: bytes, indices, seek: "WeightSeek" = None,
+                                                combination_count: int = None) -> np.ndarray:
+        """omr_retrieve_payloads_seek: the solve of decode_combined_payloads_and_solve, the matrix taken from
+        the reference's stream through the seek (None: built inside the call); no table."""
+        rp = self.params
+        cts = np.ascontiguousarray(pay_cts, dtype=np.uint64).reshape(-1, 2, N2)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        out = np.zeros((len(idx), PAYLOAD_LENGTH), np.uint16)
+        ptr, _keep = _seed_ptr(seed)
+        cc = rp.combination_count if combination_count is None else combination_count
+        _check(lib().omr_retrieve_payloads_seek(self._sk._h, cts.ctypes.data, cts.shape[0], rp.all_payloads_count, cc,
+                                                ptr, _seek_ptr(seek), idx.ctypes.data, len(idx), out.ctypes.data),
+               "omr_retrieve_payloads_seek")
         return out
 
     def decode_bitmap(self, bitmap_cts, cap: int = 1024) -> list[int]:
@@ -1051,6 +1158,19 @@ class Auditor:
                                                            out.ctypes.data), "omr_auditor_retrieve_payloads_indexed")
         return out
 
+    def retrieve_payloads_seek(self, pay_cts, all_payloads_count: int, combination_count: int, seed: bytes, indices,
+                               seek: "WeightSeek" = None, bits: int = 0) -> np.ndarray:
+        """omr_auditor_retrieve_payloads_seek: the same with the reference's weights found through the seek
+        (None: built on the auditor's device inside the call); the bits of retrieve_payloads given the table."""
+        c = self._cts(pay_cts, bits)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        out = np.zeros((len(idx), PAYLOAD_LENGTH), np.uint16)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_auditor_retrieve_payloads_seek(self._h, c.ctypes.data, c.shape[0], bits, all_payloads_count,
+                                                        combination_count, ptr, _seek_ptr(seek), idx.ctypes.data,
+                                                        len(idx), out.ctypes.data), "omr_auditor_retrieve_payloads_seek")
+        return out
+
     def decode_digest(self, idx_cts, pay_cts, seed: bytes, all_payloads_count: int, pertinent_count: int, bits: int = 0,
                       cap: int = None):
         """omr_auditor_decode_digest_indexed: Retriever.decode_digest(indexed=True) in one call on the device:
@@ -1351,6 +1471,32 @@ class Detector:
                                                         per_ct, d_out or None, stream or None),
                "omr_encode_payloads_indexed_device")
 
+    def encode_pertinent_payloads_seek(self, pertinency_vector, payloads, seed: bytes, seek: "WeightSeek",
+                                       rp: RetrievalParams, global_offset: int = 0, first_ct: int = 0,
+                                       n_ct: int = None) -> np.ndarray:
+        """omr_encode_payloads_seek: encode_pertinent_payloads' bits without its table, the reference's
+        weights found through the seek; the ciphertexts [first_ct, first_ct + n_ct) (default: all of rp's)."""
+        pv = np.ascontiguousarray(pertinency_vector, dtype=np.uint64)
+        pay = np.ascontiguousarray(payloads, dtype=np.uint16)
+        n = rp.cmb_cipher_count - first_ct if n_ct is None else n_ct
+        out = np.empty((max(n, 0), 2, N2), np.uint64)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_encode_payloads_seek(self._h, pv.ctypes.data, pay.ctypes.data, pv.shape[0], global_offset,
+                                              rp.all_payloads_count, ptr, _seek_ptr(seek), rp.combination_count,
+                                              first_ct, n, rp.cmb_count_per_cipher, out.ctypes.data),
+               "omr_encode_payloads_seek")
+        return out
+
+    def encode_pertinent_payloads_seek_device(self, d_pv: int, d_payloads: int, D: int, global_offset: int,
+                                              all_payloads_count: int, seed: bytes, seek: "WeightSeek",
+                                              combination_count: int, first_ct: int, n_ct: int, per_ct: int,
+                                              d_out: int, stream: int = 0) -> None:
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_encode_payloads_seek_device(self._h, d_pv or None, d_payloads or None, D, global_offset,
+                                                     all_payloads_count, ptr, _seek_ptr(seek), combination_count,
+                                                     first_ct, n_ct, per_ct, d_out or None, stream or None),
+               "omr_encode_payloads_seek_device")
+
     # compact ciphertexts (include/omr_gpu.h, "Compact ciphertexts"): the server side
     def compact_cts(self, cts, bits: int) -> np.ndarray:
         """omr_compact_cts: host NttRlweCiphertexts u64 [n][2][2048] -> u8 [n][512 * bits] through the device."""
@@ -1371,11 +1517,12 @@ class Detector:
         _check(lib().omr_ctx_set_compact_staging(self._h, max_ciphertexts), "omr_ctx_set_compact_staging")
 
     def digest_session(self, all_payloads_count: int, pertinent_count: int, index_seed: int, weight_seed: bytes,
-                       stream: int = 0, indexed: bool = False) -> "DigestSession":
+                       stream: int = 0, indexed: bool = False, seek: bool = False) -> "DigestSession":
         """A digest session on this detector (omr_digest_begin): detect + encode a board piece by
         piece without holding its pertinency vector. A context manager. indexed=True: a session with
-        indexed payload weights (omr_digest_begin_indexed), which holds no weight table."""
-        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream, indexed)
+        indexed payload weights (omr_digest_begin_indexed), which holds no weight table. seek=True: the
+        reference's weights without the table (omr_digest_begin_seek): the digest of the default session."""
+        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream, indexed, seek)
 
     # ---- stage entry points (benches/two_level_bs.rs) ----
     def first_level(self, clue_a, clue_b) -> np.ndarray:
@@ -1455,12 +1602,15 @@ class DigestSession:
     device and at most one detect chunk of pertinency ciphertexts is ever allocated."""
 
     def __init__(self, detector: "Detector", all_payloads_count: int, pertinent_count: int, index_seed: int,
-                 weight_seed: bytes, stream: int = 0, indexed: bool = False):
+                 weight_seed: bytes, stream: int = 0, indexed: bool = False, seek: bool = False):
         seed = np.frombuffer(bytes(weight_seed), dtype=np.uint8).copy()
         if seed.size != 32:
             raise OmrError("weight_seed must be 32 bytes")
         h = C.c_void_p()
+        if indexed and seek:
+            raise OmrError("a session uses indexed weights or the reference's weights by seek, not both")
         begin, what = ((lib().omr_digest_begin_indexed, "omr_digest_begin_indexed") if indexed else
+                       (lib().omr_digest_begin_seek, "omr_digest_begin_seek") if seek else
                        (lib().omr_digest_begin, "omr_digest_begin"))
         _check(begin(detector.handle, all_payloads_count, pertinent_count, index_seed, seed.ctypes.data,
                      stream or None, C.byref(h)), what)
