@@ -450,7 +450,9 @@ omr_status omr_encode_indices_device(omr_ctx *ctx, const uint64_t *d_pv, size_t 
                                      uint64_t seed, uint32_t first_ct, uint32_t n_ct,
                                      uint64_t *d_out /* [n_ct][2][2048] */, void *hip_stream);
 /* Detector::encode_pertinent_payloads (detector.rs:341-453). weights: omr_payload_weights()
- * output for the whole board; payloads u16 [D][612]; out u64 [n_ct][2][2048]. */
+ * output for the whole board; payloads u16 [D][612]; out u64 [n_ct][2][2048]. The device entry returns
+ * OMR_ERR_INVALID_ARGUMENT before anything is enqueued on the conditions of
+ * omr_encode_payloads_indexed_device: n_ct above 65,535 and a range beyond the board among them. */
 omr_status omr_encode_payloads(omr_ctx *ctx, const uint64_t *pv, const uint16_t *payloads,
                                size_t D, size_t global_offset, size_t all_payloads_count,
                                const uint16_t *weights, uint32_t n_ct, uint32_t cmb_per_ct,

@@ -4,6 +4,7 @@
 // boundary cases of tests/test_seek_weights_host.py (seed 23, zone 0xE0000000) and denser zones, in exactly
 // sized heap buffers (an access one word past an omr_weight_seek, an index list or a matrix is an error
 // under the sanitizer), checked against the sequential draw restated here over common.hpp's chacha_block.
+// Also the edges of common.hpp's range_on_board, the payload encode entries' range check.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -131,6 +132,13 @@ int main() {
   sk.n = OMR_WEIGHT_SEEK_MAX + 1;
   EXPECT(omr_payload_weights_at(seed, 4, 2, &sk, 0, 1, &i0, 1, &w, 1) == OMR_ERR_INVALID_ARGUMENT);
   EXPECT(omr_payload_weights_at(seed, (size_t)1 << 63, 4, &sk, 0, 1, &i0, 1, &w, 1) == OMR_ERR_INVALID_ARGUMENT);
+  // the payload encode entries' range check (common.hpp, range_on_board): offset + D wraps, an empty range at
+  // the board's end, and the last message on the board and one beyond it
+  EXPECT(!omr::range_on_board(SIZE_MAX, 2, 100));
+  EXPECT(!omr::range_on_board(SIZE_MAX, 2, SIZE_MAX));
+  EXPECT(omr::range_on_board(100, 0, 100) && !omr::range_on_board(101, 0, 100));
+  EXPECT(omr::range_on_board(40, 60, 100) && !omr::range_on_board(40, 61, 100));
+  EXPECT(omr::range_on_board(0, SIZE_MAX, SIZE_MAX) && omr::range_on_board(0, 0, 0) && !omr::range_on_board(0, 1, 0));
   if (fails) {
     std::printf("seek weights host test FAILED (%d)\n", fails);
     return 1;

@@ -123,6 +123,51 @@ def test_two_staging_rounds(det, case1):
     assert np.array_equal(got, ref)
 
 
+# ---- the staging rounds of the indexed, the table and the index kernel (the seek kernel's:
+# tests/test_gpu_seek_weights.py), which share one fold and, the payload kernels, one round loop
+ROUNDS = [(256, 2), (258, 2), (300, 1)]  # (D, set_encode_chunks): 128, 129 and 300 messages per workgroup
+ROUNDS_INDEX_SEED = 9
+
+
+@pytest.fixture(scope="module")
+def oracle_table():
+    """The oracle's weights of case 1's five combinations on its board, the padding row zero: on both sides."""
+    w = np.zeros(NCT1 * PER1 * ALL1, dtype=np.uint16)
+    w[:CC1 * ALL1] = O.payload_weights(SEED, CC1 * ALL1)[0]
+    w.setflags(write=False)
+    return w, dev(w)
+
+
+@pytest.mark.parametrize("D,chunks", ROUNDS)
+def test_staging_rounds_of_three_kernels(det, case1, oracle_table, D, chunks):
+    """The first D messages of case 1 in workgroups of exactly one staging round (128), of 128 + 1 and of
+    128 + 128 + 44: encode_payloads_indexed_kernel, encode_payloads_kernel over the oracle's table and
+    encode_indices_kernel (every index ciphertext of the board), each against the oracle."""
+    import torch
+    pv, pay = case1[0][:D], case1[1][:D]
+    w, d_w = oracle_table
+    n_idx = A.RetrievalParams(ALL1, 0).max_encode_indices_cipher_count
+    d_pv, d_pay = dev(pv), dev(pay)
+    d_tab = torch.empty((NCT1, 2, A.N2), dtype=torch.int64, device="cuda:0")
+    d_idx = torch.empty((n_idx, 2, A.N2), dtype=torch.int64, device="cuda:0")
+    det.set_encode_chunks(chunks)
+    try:
+        indexed = encode_indexed(det, pv, pay, OFF1, ALL1, CC1, 0, NCT1, PER1)
+        det.encode_payloads_device(d_pv.data_ptr(), d_pay.data_ptr(), D, OFF1, ALL1, d_w.data_ptr(), NCT1, PER1,
+                                   d_tab.data_ptr())
+        det.encode_indices_device(d_pv.data_ptr(), D, OFF1, ALL1, ROUNDS_INDEX_SEED, 0, n_idx, d_idx.data_ptr())
+        torch.cuda.synchronize()
+    finally:
+        det.set_encode_chunks(0)
+    assert np.array_equal(indexed, expected(pv, pay, OFF1, CC1, 0, NCT1, PER1)) and indexed.any()
+    table = d_tab.cpu().numpy().view(np.uint64)
+    assert np.array_equal(table, O.encode_payloads(pv, pay, OFF1, ALL1, w, NCT1, PER1)) and table.any()
+    idx = d_idx.cpu().numpy().view(np.uint64)
+    for ct in range(n_idx):
+        assert np.array_equal(idx[ct], O.encode_indices(pv, OFF1, ALL1, ROUNDS_INDEX_SEED, ct)), ct
+    assert idx.any()
+
+
 @pytest.mark.parametrize("D,off", [(1, 15), (1, 16), (17, 15), (16, 0), (33, 31)])
 def test_block_edges(det, D, off):
     """Single-message chunks and ranges that end or begin on a 16-message block edge."""

@@ -156,6 +156,45 @@ def test_messages_per_workgroup_above_and_below_a_staging_round(det, real, chunk
     assert np.array_equal(got, want) and np.array_equal(part, pwant)
 
 
+@pytest.fixture(scope="module")
+def rounds_case():
+    """Offset 12,345 of a 100,000-message board, 5 combinations in 3 ciphertexts of 2 (the sixth is padding), on
+    the real seed whose one rejection is draw 5,714: before the range in row 0, so every weight of the calls is
+    a shifted one. 300 random canonical pv and payloads, and the oracle's table with the padding row zero."""
+    import oracle_lib as O
+    all_count, off, cc, n_ct, per = 100000, 12345, 5, 3, 2
+    seed = SW.seed_of(REAL[0][0])
+    seek = A.WeightSeek.build(seed, cc * all_count, device=True)
+    assert seek.at == [REAL[0][1]] and REAL[0][1] < off
+    rng = np.random.default_rng(12345)
+    pv = rng.integers(0, A.Q2, (300, 2, A.N2), dtype=np.uint64)
+    pay = rng.integers(0, 256, (300, A.PAYLOAD_LENGTH)).astype(np.uint16)
+    w = np.zeros(n_ct * per * all_count, dtype=np.uint16)
+    w[:cc * all_count], rejected = O.payload_weights(seed, cc * all_count)
+    assert rejected == 1
+    want = {D: O.encode_payloads(pv[:D], pay[:D], off, all_count, w, n_ct, per) for D in (256, 258, 300)}
+    return (all_count, off, cc, n_ct, per, seed, seek), dev(pv), dev(pay), want
+
+
+@pytest.mark.parametrize("D,chunks", [(256, 2), (258, 2), (300, 1)])
+def test_staging_rounds_against_the_oracle(det, rounds_case, D, chunks):
+    """128 messages per workgroup (exactly one staging round), 129 (128 + 1) and 300 (128 + 128 + 44): the seek
+    kernel against the oracle's encode over the oracle's table. The other three encode kernels at these
+    shapes: tests/test_gpu_indexed_weights.py."""
+    import torch
+    (all_count, off, cc, n_ct, per, seed, seek), d_pv, d_pay, want = rounds_case
+    d_out = torch.full((n_ct, 2, A.N2), -1, dtype=torch.int64, device="cuda:0")
+    det.set_encode_chunks(chunks)
+    try:
+        det.encode_pertinent_payloads_seek_device(d_pv.data_ptr(), d_pay.data_ptr(), D, off, all_count, seed, seek, cc,
+                                                  0, n_ct, per, d_out.data_ptr())
+        torch.cuda.synchronize()
+    finally:
+        det.set_encode_chunks(0)
+    got = d_out.cpu().numpy().view(np.uint64)
+    assert np.array_equal(got, want[D]) and got.any()
+
+
 def test_ciphertext_groups(det, real):
     c, i = real
     full, _ = encode_both(det, c, 0, c.all)

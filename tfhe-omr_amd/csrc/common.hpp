@@ -102,6 +102,9 @@ OMR_HD void indexed_weight_block(const WeightKey &key, uint32_t j, uint64_t bloc
 // Error reporting (thread-local message behind omr_last_error()).
 omr_status set_error(omr_status st, const std::string &msg);
 
+// The messages [offset, offset + D) lie on a board of `all`: no sum that could wrap.
+inline bool range_on_board(size_t offset, size_t D, size_t all) { return offset <= all && D <= all - offset; }
+
 // Reference payload weights by seek (include/omr_gpu.h, "Reference payload weights by seek"): the
 // statement that the builders, omr_payload_weights_at, the seek encode kernel and the auditor's matrix
 // kernel share. The stream is omr_payload_weights': ChaCha12, stream id 0, raw position r = word r & 15

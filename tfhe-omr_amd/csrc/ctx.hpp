@@ -207,26 +207,25 @@ omr_status detect_device(omr_ctx *c, const uint16_t *d_clue_a, const uint16_t *d
 omr_status detect_host(omr_ctx *c, const uint16_t *clue_a, const uint16_t *clue_b, size_t D, uint64_t *out);
 omr_status take_handoff_error(omr_ctx *c);
 
-// encode.hip. The bodies of omr_encode_indices_device / omr_encode_payloads_device after their
+// encode.hip. The bodies of omr_encode_indices_device / omr_encode_payloads*_device after their
 // argument checks. accumulate = false: out = the sum of the chunk partials (the public entry points);
 // accumulate = true: out = (out + that sum) mod q2, out canonical before and after (the digest
 // session); D = 0 then leaves out alone.
 omr_status encode_indices(omr_ctx *c, const uint64_t *d_pv, size_t D, size_t offset, size_t all, uint64_t seed,
                           uint32_t first_ct, uint32_t n_ct, uint64_t *d_out, hipStream_t st, bool accumulate);
+// Where a payload encode takes its weights from, one kind per device entry point and digest session.
+struct PayloadWeights {
+  enum Kind { TABLE, INDEXED, SEEK } kind = TABLE;
+  const uint16_t *d_table = nullptr;  // TABLE: [n_ct * per_ct][all] on the device, row 0 = first_ct's first
+  WeightKey key{};                    // INDEXED (common.hpp, indexed_weight_block), SEEK: the weight seed
+  omr_weight_seek seek{};             // SEEK (common.hpp, "Reference payload weights by seek"): of combos * all draws
+  uint32_t combos = 0;                // INDEXED, SEEK: combinations from this one on are padding, weight 0
+};
+// The body of the three omr_encode_payloads*_device entries: the ciphertexts [first_ct, first_ct + n_ct) of
+// per_ct combinations each; the kind picks the kernel (encode_kernels.hpp).
 omr_status encode_payloads(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D, size_t offset,
-                           size_t all, const uint16_t *d_weights, uint32_t n_ct, uint32_t per_ct, uint64_t *d_out,
-                           hipStream_t st, bool accumulate);
-// The body of omr_encode_payloads_indexed_device: as encode_payloads, the weights computed in the kernel
-// from the key (common.hpp, indexed_weight_block) for the ciphertexts [first_ct, first_ct + n_ct).
-omr_status encode_payloads_indexed(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D,
-                                   size_t offset, const WeightKey &key, uint32_t combos, uint32_t first_ct,
-                                   uint32_t n_ct, uint32_t per_ct, uint64_t *d_out, hipStream_t st, bool accumulate);
-// The body of omr_encode_payloads_seek_device: as encode_payloads_indexed, the reference's weights found
-// through the seek (common.hpp, "Reference payload weights by seek"), which covers combos * all draws.
-omr_status encode_payloads_seek(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D, size_t offset,
-                                size_t all, const WeightKey &key, const omr_weight_seek &seek, uint32_t combos,
-                                uint32_t first_ct, uint32_t n_ct, uint32_t per_ct, uint64_t *d_out, hipStream_t st,
-                                bool accumulate);
+                           size_t all, const PayloadWeights &weights, uint32_t first_ct, uint32_t n_ct,
+                           uint32_t per_ct, uint64_t *d_out, hipStream_t st, bool accumulate);
 // The body of omr_encode_bitmap_device after its argument checks (bitmap_kernel.hpp): d_out is the whole
 // board's [omr_bitmap_ct_count(all)][2][N2]. accumulate = false: the touched ciphertexts are the sums of
 // their partials and the others zero; accumulate = true: the touched ones are added into, the others

@@ -30,10 +30,8 @@ struct omr_digest {
   size_t all;
   uint64_t index_seed;
   omr_retrieval_params rp;
-  DevBuf<uint16_t> weights;      // [payload_ct * cmb_count_per_cipher][all]; only a table session has them
-  enum Weights { TABLE, INDEXED, SEEK } source = TABLE;  // omr_digest_begin, _begin_indexed, _begin_seek
-  WeightKey wkey{};              // INDEXED, SEEK: the weights come from wkey in the kernel
-  omr_weight_seek seek{};        // SEEK: the rejections of the board's combination_count * all draws
+  DevBuf<uint16_t> table;        // [payload_ct * cmb_count_per_cipher][all]; only a table session has them
+  PayloadWeights weights;        // TABLE, INDEXED, SEEK: omr_digest_begin, _begin_indexed, _begin_seek
   DevBuf<uint64_t> digest;       // [index_ct + payload_ct][2][N2], canonical
   DevBuf<uint64_t> pv;           // pertinency ciphertexts of one piece, grown lazily
   DevBuf<uint64_t> merge_stage;  // omr_digest_merge's and omr_digest_merge_bitmap's upload
@@ -89,13 +87,7 @@ omr_status run_piece(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, con
   if (dg->n_bmp) OMR_TRY(encode_bitmap(c, dg->pv, n, offset, dg->all, dg->bitmap, st, true));
   OMR_TRY(encode_indices(c, dg->pv, n, offset, dg->all, dg->index_seed, 0, dg->n_idx(), dg->digest, st, true));
   uint64_t *pay_digest = dg->digest + (size_t)dg->n_idx() * 2 * N2;
-  if (dg->source == omr_digest::SEEK)
-    return encode_payloads_seek(c, dg->pv, pay, n, offset, dg->all, dg->wkey, dg->seek, dg->rp.combination_count, 0,
-                                dg->n_pay(), dg->rp.cmb_count_per_cipher, pay_digest, st, true);
-  if (dg->source == omr_digest::INDEXED)
-    return encode_payloads_indexed(c, dg->pv, pay, n, offset, dg->wkey, dg->rp.combination_count, 0, dg->n_pay(),
-                                   dg->rp.cmb_count_per_cipher, pay_digest, st, true);
-  return encode_payloads(c, dg->pv, pay, n, offset, dg->all, dg->weights, dg->n_pay(), dg->rp.cmb_count_per_cipher,
+  return encode_payloads(c, dg->pv, pay, n, offset, dg->all, dg->weights, 0, dg->n_pay(), dg->rp.cmb_count_per_cipher,
                          pay_digest, st, true);
 }
 
@@ -141,7 +133,7 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
 // omr_digest_begin, omr_digest_begin_indexed and omr_digest_begin_seek: only the table session draws and
 // uploads weights; the seek session scans the stream for its rejections on the device.
 omr_status digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed, const uint8_t weight_seed[32],
-                        void *stream, omr_digest **out, omr_digest::Weights source, const char *who) {
+                        void *stream, omr_digest **out, PayloadWeights::Kind kind, const char *who) {
   if (!c || !weight_seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
   *out = nullptr;
   omr_retrieval_params rp;
@@ -151,20 +143,23 @@ omr_status digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index
   try {
     std::unique_ptr<omr_digest> dg(new omr_digest(c, (hipStream_t)stream, all, index_seed));
     dg->rp = rp;
-    dg->source = source;
-    if (source != omr_digest::TABLE) {
-      dg->wkey = weight_key(weight_seed);
-      if (source == omr_digest::SEEK) {
+    PayloadWeights &pw = dg->weights;
+    pw.kind = kind;
+    pw.combos = rp.combination_count;
+    if (kind != PayloadWeights::TABLE) {
+      pw.key = weight_key(weight_seed);
+      if (kind == PayloadWeights::SEEK) {
         if (all > SEEK_MAX_DRAWS / ((uint64_t)rp.combination_count + 1))
           return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": board too large");
-        OMR_TRY(omr_weight_seek_build_device(weight_seed, (uint64_t)rp.combination_count * all, &dg->seek, stream));
+        OMR_TRY(omr_weight_seek_build_device(weight_seed, (uint64_t)rp.combination_count * all, &pw.seek, stream));
       }
     } else {
       std::vector<uint16_t> w((size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * all);
       if ((s = omr_payload_weights(weight_seed, all, rp.combination_count, rp.cmb_cipher_count,
                                    rp.cmb_count_per_cipher, w.data())) != OMR_OK)
         return s;
-      HIP_TRY(dg->weights.upload_sync(w));
+      HIP_TRY(dg->table.upload_sync(w));
+      pw.d_table = dg->table;
     }
     HIP_TRY(dg->digest.alloc(dg->digest_elems()));
     HIP_TRY(hipMemsetAsync(dg->digest, 0, dg->digest_elems() * sizeof(uint64_t), dg->st));
@@ -180,18 +175,18 @@ omr_status digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index
 
 extern "C" omr_status omr_digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
                                        const uint8_t weight_seed[32], void *stream, omr_digest **out) {
-  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, omr_digest::TABLE, "omr_digest_begin");
+  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, PayloadWeights::TABLE, "omr_digest_begin");
 }
 
 extern "C" omr_status omr_digest_begin_indexed(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
                                                const uint8_t weight_seed[32], void *stream, omr_digest **out) {
-  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, omr_digest::INDEXED,
+  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, PayloadWeights::INDEXED,
                       "omr_digest_begin_indexed");
 }
 
 extern "C" omr_status omr_digest_begin_seek(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
                                             const uint8_t weight_seed[32], void *stream, omr_digest **out) {
-  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, omr_digest::SEEK, "omr_digest_begin_seek");
+  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, PayloadWeights::SEEK, "omr_digest_begin_seek");
 }
 
 extern "C" omr_status omr_digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
@@ -362,7 +357,7 @@ extern "C" omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info)
 extern "C" omr_status omr_digest_device_bytes(omr_digest *dg, size_t *total, size_t *weights) {
   if (!dg || !total || !weights) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_device_bytes: NULL argument");
   std::lock_guard<std::mutex> lk(dg->mu);
-  *weights = dg->weights.capacity() * sizeof(uint16_t);
+  *weights = dg->table.capacity() * sizeof(uint16_t);
   *total = *weights + (dg->digest.capacity() + dg->pv.capacity() + dg->merge_stage.capacity() + dg->bitmap.capacity()) *
                           sizeof(uint64_t) +
            dg->compact.capacity() * sizeof(uint32_t) +

@@ -70,31 +70,25 @@ omr_status omr::encode_indices(omr_ctx *c, const uint64_t *pv, size_t D, size_t 
 }
 
 omr_status omr::encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, size_t offset,
-                                size_t all, const uint16_t *weights, uint32_t n_ct, uint32_t per_ct, uint64_t *out,
-                                hipStream_t st, bool accumulate) {
+                                size_t all, const PayloadWeights &w, uint32_t first_ct, uint32_t n_ct, uint32_t per_ct,
+                                uint64_t *out, hipStream_t st, bool accumulate) {
   return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
-    encode_payloads_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, weights, (int)per_ct, per_wg,
-                                                   c->tab.tb.tw2, c->scr.partial);
-  });
-}
-
-omr_status omr::encode_payloads_indexed(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
-                                        size_t offset, const WeightKey &key, uint32_t combos, uint32_t first_ct,
-                                        uint32_t n_ct, uint32_t per_ct, uint64_t *out, hipStream_t st,
-                                        bool accumulate) {
-  return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
-    encode_payloads_indexed_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, key, combos, first_ct,
-                                                           (int)per_ct, per_wg, c->tab.tb.tw2, c->scr.partial);
-  });
-}
-
-omr_status omr::encode_payloads_seek(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, size_t offset,
-                                     size_t all, const WeightKey &key, const omr_weight_seek &seek, uint32_t combos,
-                                     uint32_t first_ct, uint32_t n_ct, uint32_t per_ct, uint64_t *out, hipStream_t st,
-                                     bool accumulate) {
-  return encode_chunked(c, D, n_ct, out, st, accumulate, [&](dim3 grid, int per_wg) {
-    encode_payloads_seek_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, key, seek, combos, first_ct,
-                                                        (int)per_ct, per_wg, c->tab.tb.tw2, c->scr.partial);
+    const double *tw = c->tab.tb.tw2;
+    uint64_t *partial = c->scr.partial;
+    switch (w.kind) {
+      case PayloadWeights::TABLE:
+        encode_payloads_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, w.d_table, (int)per_ct,
+                                                       per_wg, tw, partial);
+        break;
+      case PayloadWeights::INDEXED:
+        encode_payloads_indexed_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, w.key, w.combos, first_ct,
+                                                               (int)per_ct, per_wg, tw, partial);
+        break;
+      case PayloadWeights::SEEK:
+        encode_payloads_seek_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, w.key, w.seek, w.combos,
+                                                            first_ct, (int)per_ct, per_wg, tw, partial);
+        break;
+    }
   });
 }
 
@@ -135,6 +129,47 @@ omr_status omr::encode_bitmap(omr_ctx *c, const uint64_t *pv, size_t D, size_t o
   return lease.release();
 }
 
+namespace {
+// The one argument check of the three payload device entries, `source` being the entry's own weight
+// arguments: n_ct is the grid's y extent, D the kernels' int.
+omr_status check_payload_args(const char *who, const omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
+                              bool source, size_t D, size_t offset, size_t all, uint32_t n_ct, uint32_t per_ct,
+                              const uint64_t *out) {
+  if (!c || !out || !source || (D && (!pv || !payloads)) || n_ct == 0 || n_ct > 65535 || per_ct == 0 ||
+      per_ct * PAYLOAD_LEN > (uint32_t)N2 || !range_on_board(offset, D, all) || D > (size_t)INT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": bad argument");
+  return OMR_OK;
+}
+// The three entries after their checks. stream NULL: HIP's null stream.
+omr_status encode_payloads_locked(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, size_t offset,
+                                  size_t all, const PayloadWeights &w, uint32_t first_ct, uint32_t n_ct,
+                                  uint32_t per_ct, uint64_t *out, void *stream) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  return encode_payloads(c, pv, payloads, D, offset, all, w, first_ct, n_ct, per_ct, out, (hipStream_t)stream, false);
+}
+// The host-buffer entries' common path: pv (and the payloads, when the entry has them) uploaded, run(d_pv,
+// d_payloads, d_out) = the device entry on c->stream, and its n_ct ciphertexts downloaded once it is done.
+template <typename Run>
+omr_status encode_from_host(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, uint32_t n_ct,
+                            uint64_t *out, Run run) {
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<uint64_t> dpv, dout;
+  DevBuf<uint16_t> dpay;
+  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
+  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
+  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+  if (payloads) {
+    HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
+    HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  OMR_TRY(run((const uint64_t *)dpv, (const uint16_t *)dpay, (uint64_t *)dout));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return OMR_OK;
+}
+}  // namespace
+
 extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, size_t D,
                                                 size_t offset, size_t all, uint64_t seed,
                                                 uint32_t first_ct, uint32_t n_ct, uint64_t *out,
@@ -151,27 +186,19 @@ extern "C" omr_status omr_encode_payloads_device(omr_ctx *c, const uint64_t *pv,
                                                  const uint16_t *payloads, size_t D, size_t offset,
                                                  size_t all, const uint16_t *weights, uint32_t n_ct,
                                                  uint32_t per_ct, uint64_t *out, void *stream) {
-  if (!c || !out || (D && (!pv || !payloads || !weights)) || n_ct == 0 || per_ct == 0 ||
-      per_ct * PAYLOAD_LEN > (uint32_t)N2 || offset + D > all || D > (size_t)INT32_MAX)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_device: bad argument");
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  // NULL: HIP's null stream
-  return encode_payloads(c, pv, payloads, D, offset, all, weights, n_ct, per_ct, out, (hipStream_t)stream, false);
+  OMR_TRY(check_payload_args("omr_encode_payloads_device", c, pv, payloads, weights || !D, D, offset, all, n_ct, per_ct,
+                             out));
+  PayloadWeights w;
+  w.d_table = weights;
+  return encode_payloads_locked(c, pv, payloads, D, offset, all, w, 0, n_ct, per_ct, out, stream);
 }
 
 extern "C" omr_status omr_encode_indices(omr_ctx *c, const uint64_t *pv, size_t D, size_t offset,
                                          size_t all, uint64_t seed, uint32_t ct, uint64_t *out) {
   if (!c || !out || (D && !pv)) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_indices");
-  HIP_TRY(hipSetDevice(c->device));
-  DevBuf<uint64_t> dpv, dout;
-  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
-  HIP_TRY(dout.alloc(2 * N2));
-  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
-  OMR_TRY(omr_encode_indices_device(c, dpv, D, offset, all, seed, ct, 1, dout, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(out, dout, 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return OMR_OK;
+  return encode_from_host(c, pv, nullptr, D, 1, out, [&](const uint64_t *dpv, const uint16_t *, uint64_t *dout) {
+    return omr_encode_indices_device(c, dpv, D, offset, all, seed, ct, 1, dout, c->stream);
+  });
 }
 
 extern "C" omr_status omr_encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
@@ -182,34 +209,24 @@ extern "C" omr_status omr_encode_payloads(omr_ctx *c, const uint64_t *pv, const 
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads");
   HIP_TRY(hipSetDevice(c->device));
   const size_t wn = (size_t)n_ct * per_ct * all;
-  DevBuf<uint64_t> dpv, dout;
-  DevBuf<uint16_t> dpay, dw;
-  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
-  HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
+  DevBuf<uint16_t> dw;
   HIP_TRY(dw.alloc(std::max<size_t>(wn, 1)));
-  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
-  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dw, weights, wn * sizeof(uint16_t), hipMemcpyHostToDevice));
-  OMR_TRY(omr_encode_payloads_device(c, dpv, dpay, D, offset, all, dw, n_ct, per_ct, dout, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return OMR_OK;
+  auto run = [&](const uint64_t *dpv, const uint16_t *dpay, uint64_t *dout) {
+    return omr_encode_payloads_device(c, dpv, dpay, D, offset, all, dw, n_ct, per_ct, dout, c->stream);
+  };
+  return encode_from_host(c, pv, payloads, D, n_ct, out, run);
 }
 
 extern "C" omr_status omr_encode_payloads_indexed_device(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
                                                          size_t D, size_t offset, size_t all, const uint8_t seed[32],
                                                          uint32_t combos, uint32_t first_ct, uint32_t n_ct,
                                                          uint32_t per_ct, uint64_t *out, void *stream) {
-  if (!c || !out || !seed || (D && (!pv || !payloads)) || n_ct == 0 || per_ct == 0 ||
-      per_ct * PAYLOAD_LEN > (uint32_t)N2 || offset > all || D > all - offset || D > (size_t)INT32_MAX ||
-      n_ct > 65535)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_indexed_device: bad argument");
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  // NULL: HIP's null stream
-  return encode_payloads_indexed(c, pv, payloads, D, offset, weight_key(seed), combos, first_ct, n_ct, per_ct, out,
-                                 (hipStream_t)stream, false);
+  OMR_TRY(check_payload_args("omr_encode_payloads_indexed_device", c, pv, payloads, seed != nullptr, D, offset, all,
+                             n_ct, per_ct, out));
+  PayloadWeights w;
+  w.kind = PayloadWeights::INDEXED, w.key = weight_key(seed), w.combos = combos;
+  return encode_payloads_locked(c, pv, payloads, D, offset, all, w, first_ct, n_ct, per_ct, out, stream);
 }
 
 extern "C" omr_status omr_encode_payloads_indexed(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
@@ -217,19 +234,11 @@ extern "C" omr_status omr_encode_payloads_indexed(omr_ctx *c, const uint64_t *pv
                                                   uint32_t first_ct, uint32_t n_ct, uint32_t per_ct, uint64_t *out) {
   if (!c || !out || !seed || (D && (!pv || !payloads)) || n_ct == 0)
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_indexed");
-  HIP_TRY(hipSetDevice(c->device));
-  DevBuf<uint64_t> dpv, dout;
-  DevBuf<uint16_t> dpay;
-  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
-  HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
-  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
-  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
-  OMR_TRY(omr_encode_payloads_indexed_device(c, dpv, dpay, D, offset, all, seed, combos, first_ct, n_ct, per_ct, dout,
-                                             c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return OMR_OK;
+  auto run = [&](const uint64_t *dpv, const uint16_t *dpay, uint64_t *dout) {
+    return omr_encode_payloads_indexed_device(c, dpv, dpay, D, offset, all, seed, combos, first_ct, n_ct, per_ct, dout,
+                                              c->stream);
+  };
+  return encode_from_host(c, pv, payloads, D, n_ct, out, run);
 }
 
 extern "C" omr_status omr_indexed_weights_table_device(const uint8_t seed[32], size_t all, uint32_t combos,
@@ -250,18 +259,14 @@ extern "C" omr_status omr_encode_payloads_seek_device(omr_ctx *c, const uint64_t
                                                       size_t D, size_t offset, size_t all, const uint8_t seed[32],
                                                       const omr_weight_seek *seek, uint32_t combos, uint32_t first_ct,
                                                       uint32_t n_ct, uint32_t per_ct, uint64_t *out, void *stream) {
-  if (!c || !out || !seed || !seek || (D && (!pv || !payloads)) || n_ct == 0 || per_ct == 0 ||
-      per_ct * PAYLOAD_LEN > (uint32_t)N2 || offset > all || D > all - offset || D > (size_t)INT32_MAX ||
-      n_ct > 65535)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_seek_device: bad argument");
+  OMR_TRY(check_payload_args("omr_encode_payloads_seek_device", c, pv, payloads, seed && seek, D, offset, all, n_ct,
+                             per_ct, out));
   if (!seek_covers(seek, combos, all))
     return set_error(OMR_ERR_INVALID_ARGUMENT,
                      "omr_encode_payloads_seek_device: the seek does not cover combination_count * all draws");
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  // NULL: HIP's null stream
-  return encode_payloads_seek(c, pv, payloads, D, offset, all, weight_key(seed), *seek, combos, first_ct, n_ct, per_ct,
-                              out, (hipStream_t)stream, false);
+  PayloadWeights w;
+  w.kind = PayloadWeights::SEEK, w.key = weight_key(seed), w.seek = *seek, w.combos = combos;
+  return encode_payloads_locked(c, pv, payloads, D, offset, all, w, first_ct, n_ct, per_ct, out, stream);
 }
 
 extern "C" omr_status omr_encode_payloads_seek(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
@@ -270,19 +275,11 @@ extern "C" omr_status omr_encode_payloads_seek(omr_ctx *c, const uint64_t *pv, c
                                                uint32_t n_ct, uint32_t per_ct, uint64_t *out) {
   if (!c || !out || !seed || !seek || (D && (!pv || !payloads)) || n_ct == 0)
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_seek");
-  HIP_TRY(hipSetDevice(c->device));
-  DevBuf<uint64_t> dpv, dout;
-  DevBuf<uint16_t> dpay;
-  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
-  HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
-  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
-  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
-  OMR_TRY(omr_encode_payloads_seek_device(c, dpv, dpay, D, offset, all, seed, seek, combos, first_ct, n_ct, per_ct, dout,
-                                          c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return OMR_OK;
+  auto run = [&](const uint64_t *dpv, const uint16_t *dpay, uint64_t *dout) {
+    return omr_encode_payloads_seek_device(c, dpv, dpay, D, offset, all, seed, seek, combos, first_ct, n_ct, per_ct,
+                                           dout, c->stream);
+  };
+  return encode_from_host(c, pv, payloads, D, n_ct, out, run);
 }
 
 // The device builder of a seek: weight_seek_scan_kernel over the raw words [0, draws + OMR_WEIGHT_SEEK_MAX] on
@@ -330,13 +327,7 @@ extern "C" omr_status omr_encode_bitmap(omr_ctx *c, const uint64_t *pv, size_t D
   uint32_t n_ct;
   if (!c || !out || (D && !pv)) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_bitmap");
   OMR_TRY(omr_bitmap_ct_count(all, &n_ct));
-  HIP_TRY(hipSetDevice(c->device));
-  DevBuf<uint64_t> dpv, dout;
-  HIP_TRY(dpv.alloc(std::max<size_t>(D, 1) * 2 * N2));
-  HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
-  HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
-  OMR_TRY(omr_encode_bitmap_device(c, dpv, D, offset, all, dout, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(out, dout, (size_t)n_ct * 2 * N2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return OMR_OK;
+  return encode_from_host(c, pv, nullptr, D, n_ct, out, [&](const uint64_t *dpv, const uint16_t *, uint64_t *dout) {
+    return omr_encode_bitmap_device(c, dpv, D, offset, all, dout, c->stream);
+  });
 }
