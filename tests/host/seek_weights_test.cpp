@@ -1,9 +1,10 @@
-// Stand-alone host test of the reference payload weights by seek (csrc/keygen.hip: omr_weight_seek_build_cpu,
-// its zone stage entry and omr_payload_weights_at), meant for a build with csrc/keygen.hip under the address
-// and undefined-behaviour sanitizers (make build/seek_weights_test; no GPU is touched). The overflow and
+// Stand-alone host test of the reference payload weights by seek (csrc/weights.hip: omr_weight_seek_build_cpu,
+// its zone stage entry and omr_payload_weights_at), meant for a build with csrc/weights.hip and csrc/keygen.hip
+// under the address and undefined-behaviour sanitizers (make build/seek_weights_test; no GPU is touched). The overflow and
 // boundary cases of tests/test_seek_weights_host.py (seed 23, zone 0xE0000000) and denser zones, in exactly
 // sized heap buffers (an access one word past an omr_weight_seek, an index list or a matrix is an error
 // under the sanitizer), checked against the sequential draw restated here over common.hpp's chacha_block.
+// omr_indexed_weights_at, which shares omr_payload_weights_at's row loop, against omr_indexed_weights_table.
 // Also the edges of common.hpp's range_on_board, the payload encode entries' range check.
 #include <cstdio>
 #include <cstdlib>
@@ -90,10 +91,47 @@ void check(uint64_t lo, uint32_t zone, uint64_t draws, const char *name) {
   }
 }
 
+// omr_indexed_weights_at on unsorted indices that come back to a block they left, with one padding
+// combination, into an exactly sized matrix: the gather from omr_indexed_weights_table's rows.
+void check_indexed() {
+  uint8_t seed[32];
+  seed_of(77, seed);
+  const size_t all = 40;
+  const uint32_t combos = 3, rows = 4;  // two ciphertexts of two combinations: row 3 is padding
+  const size_t list[] = {33, 2, 17, 35, 0, 39, 16, 2};  // blocks 2, 0, 1, 2, 0, 2, 1, 0
+  const size_t n = sizeof list / sizeof list[0];
+  uint16_t *table = (uint16_t *)std::malloc(rows * all * sizeof(uint16_t));
+  size_t *idx = (size_t *)std::malloc(sizeof list);
+  std::memcpy(idx, list, sizeof list);
+  EXPECT(omr_indexed_weights_table(seed, all, combos, 2, 2, table, 1) == OMR_OK);
+  for (int nthreads : {1, 3}) {
+    uint16_t *m = (uint16_t *)std::malloc(rows * n * sizeof(uint16_t));
+    std::memset(m, 0xAB, rows * n * sizeof(uint16_t));
+    EXPECT(omr_indexed_weights_at(seed, combos, 0, rows, idx, n, m, nthreads) == OMR_OK);
+    bool same = true, live = false;
+    for (size_t j = 0; j < rows; ++j)
+      for (size_t k = 0; k < n; ++k) {
+        same = same && m[j * n + k] == table[j * all + idx[k]];
+        live = live || m[j * n + k] != 0;
+      }
+    for (size_t k = 0; k < n; ++k) same = same && m[(size_t)combos * n + k] == 0;  // the padding row
+    EXPECT(same && live);
+    // a window that starts at the last real combination
+    EXPECT(omr_indexed_weights_at(seed, combos, 2, 2, idx, n, m, nthreads) == OMR_OK);
+    for (size_t j = 0; j < 2; ++j)
+      for (size_t k = 0; k < n; ++k) same = same && m[j * n + k] == table[(2 + j) * all + idx[k]];
+    EXPECT(same);
+    std::free(m);
+  }
+  std::free(idx);
+  std::free(table);
+}
+
 }  // namespace
 
 int main() {
   const uint32_t Z = 0xE0000000u;
+  check_indexed();
   for (uint64_t d : {0, 1, 2, 9, 10, 11, 84, 85, 86, 184, 185, 186, 213}) check(23, Z, d, "seed 23 edges");
   for (uint64_t d : {214, 215, 216}) check(23, Z, d, "exactly 32");
   for (uint64_t d : {217, 226, 227, 300, 4096, 70000}) check(23, Z, d, "overflow");

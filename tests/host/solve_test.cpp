@@ -1,6 +1,6 @@
 // Stand-alone host test of the mod-257 solve's CPU statement (csrc/retriever.hip: omr_solve_mod257_cpu), meant
-// for a build with csrc/keygen.hip under the address and undefined-behaviour sanitizers (make build/solve_test;
-// no GPU is touched): the crafted systems of tests/solve_cases.py restated here in exactly sized heap buffers
+// for a build with csrc/weights.hip and csrc/keygen.hip under the address and undefined-behaviour sanitizers
+// (make build/solve_test; no GPU is touched): the crafted systems of tests/solve_cases.py restated here in exactly sized heap buffers
 // (an access one word past a row or a buffer is an error under the sanitizer), checked against a plain
 // restatement of the definition, the threaded row updates, the singular reports and the argument errors.
 #include <cstdio>

@@ -141,6 +141,36 @@ def test_errors_are_the_cpu_twins(board):
         dev = L.omr_auditor_retrieve_payloads_indexed(aud._h, pay.ctypes.data, n_ct, 0, ALL, cc, seed.ctypes.data,
                                                       ix.ctypes.data, len(ix), out.ctypes.data)
         assert cpu == dev == 1 and L.omr_last_error().decode().endswith(cpu_msg), kw
+    # the same three, and a seek one draw short, on every kind of matrix source: the table, the indexed weights,
+    # the reference's weights through a given seek and through a NULL one (all refused before the decode)
+    table = np.ascontiguousarray(board.weights, dtype=np.uint16).reshape(-1)
+    whole = A.WeightSeek.for_board(WEIGHT_SEED, rp)
+    short = A.WeightSeek.build(WEIGHT_SEED, rp.combination_count * ALL - 1)
+    raw = C.CDLL(A.LIB_PATH)  # prototypes of plain pointers for the three host entries
+    p, z, u32 = C.c_void_p, C.c_size_t, C.c_uint32
+    raw.omr_retrieve_payloads.argtypes = raw.omr_retrieve_payloads_indexed.argtypes = [p, p, u32, z, u32, p, p, z, p]
+    raw.omr_retrieve_payloads_seek.argtypes = [p, p, u32, z, u32, p, p, p, z, p]
+    three = (dict(n_ct=1), dict(cc=3), dict(idx=np.array([1, 2, ALL], dtype=np.uintp)))
+    for kind, cases in (("table", three), ("indexed", three), ("seek", three + (dict(seek=short),)), ("seek_null", three)):
+        for kw in cases:
+            n_ct, cc, ix = kw.get("n_ct", pay.shape[0]), kw.get("cc", rp.combination_count), kw.get("idx", idx)
+            src = table.ctypes.data if kind == "table" else seed.ctypes.data
+            front = (pay.ctypes.data, n_ct, ALL, cc, src)
+            back = (ix.ctypes.data, len(ix), out.ctypes.data)
+            if kind in ("table", "indexed"):
+                name = "omr_retrieve_payloads" + ("" if kind == "table" else "_indexed")
+                cpu = getattr(raw, name)(board.sk._h, *front, *back)
+                cpu_msg = L.omr_last_error().decode().split(": ", 1)[1]
+                dev = getattr(L, name.replace("omr_", "omr_auditor_"))(aud._h, pay.ctypes.data, n_ct, 0, ALL, cc, src, *back)
+            else:
+                sk = None if kind == "seek_null" else kw.get("seek", whole).ptr
+                cpu = raw.omr_retrieve_payloads_seek(board.sk._h, *front, sk, *back)
+                cpu_msg = L.omr_last_error().decode().split(": ", 1)[1]
+                dev = L.omr_auditor_retrieve_payloads_seek(aud._h, pay.ctypes.data, n_ct, 0, ALL, cc, src, sk, *back)
+            dev_msg = L.omr_last_error().decode()
+            assert cpu == dev == 1 and dev_msg.split(": ", 1)[1] == cpu_msg, (kind, kw, dev_msg)
+            assert dev_msg.startswith("omr_auditor_retrieve_payloads"), (kind, kw, dev_msg)
+    assert cpu_msg == "index out of range" and not out.any()
     # bits out of range, NULL arguments, more rows than the solver takes
     with pytest.raises(A.OmrError, match=INVALID_ARGUMENT):
         aud.retrieve_payloads_indexed(board.pay["indexed"][24], ALL, rp.combination_count, WEIGHT_SEED, PERTINENT, bits=15)

@@ -221,7 +221,7 @@ def test_draws_bound_on_the_host_consumers(board):
 
 def test_sanitizer_program():
     """tests/host/seek_weights_test.cpp: the CPU builder and omr_payload_weights_at on the overflow and
-    boundary cases in exactly sized heap buffers, compiled with keygen.hip under the address and
+    boundary cases in exactly sized heap buffers, compiled with weights.hip and keygen.hip under the address and
     undefined-behaviour sanitizers (host code, no GPU)."""
     pkg = os.path.join(PL.ROOT, "tfhe-omr_amd")
     subprocess.run(["make", "-s", "-C", pkg, "build/seek_weights_test"], check=True)

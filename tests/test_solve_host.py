@@ -187,7 +187,7 @@ def test_retrieve_payloads_equal_the_solve_on_the_same_system(digest, kind):
 def test_sanitized_host_program():
     """tests/host/solve_test.cpp: the CPU entry over crafted systems in exactly sized buffers (the panel-edge
     ones placed by the panel width given on its command line), compiled with
-    retriever.hip and keygen.hip under the address and undefined-behaviour sanitizers (host code, no GPU)."""
+    retriever.hip, weights.hip and keygen.hip under the address and undefined-behaviour sanitizers (host code, no GPU)."""
     pkg = os.path.join(PL.ROOT, "tfhe-omr_amd")
     subprocess.run(["make", "-s", "-C", pkg, "build/solve_test"], check=True)
     r = subprocess.run([os.path.join(pkg, "build", "solve_test"), str(GEOM["panel_cols"])], capture_output=True,

@@ -7,6 +7,8 @@
 //   encode.hip    the encode kernels' launches and entry points
 //   digest.hip    the digest session over detect and encode
 //   compact.hip   compact ciphertexts: both kernels' launches (lent through compact.hpp), the context's entry points
+// Beside them, without the context: weights.hip (the host weight functions over weights.hpp's statement, which
+// the kernels share) and the recipient's retriever.hip and retrieve_device.hip over retrieve_system.hpp.
 // One rule for kernels: a non-template __global__ function lives in a header that exactly one of these
 // includes (or in the .hip itself); a second includer would define its host stub twice and the link
 // fails. Headers that several units share (kernels.hpp, device_*.hpp, fft1024.hpp, exactness.hpp,
@@ -20,6 +22,7 @@
 
 #include "hip_util.hpp"
 #include "kernels.hpp"
+#include "weights.hpp"
 
 #ifndef OMR_DEFAULT_LATENCY_MAX
 #define OMR_DEFAULT_LATENCY_MAX 64  // chunks up to this many messages run the latency kernels
@@ -217,8 +220,8 @@ omr_status encode_indices(omr_ctx *c, const uint64_t *d_pv, size_t D, size_t off
 struct PayloadWeights {
   enum Kind { TABLE, INDEXED, SEEK } kind = TABLE;
   const uint16_t *d_table = nullptr;  // TABLE: [n_ct * per_ct][all] on the device, row 0 = first_ct's first
-  WeightKey key{};                    // INDEXED (common.hpp, indexed_weight_block), SEEK: the weight seed
-  omr_weight_seek seek{};             // SEEK (common.hpp, "Reference payload weights by seek"): of combos * all draws
+  WeightKey key{};                    // INDEXED (weights.hpp, indexed_weight_block), SEEK: the weight seed
+  omr_weight_seek seek{};             // SEEK (weights.hpp, "Reference payload weights by seek"): of combos * all draws
   uint32_t combos = 0;                // INDEXED, SEEK: combinations from this one on are padding, weight 0
 };
 // The body of the three omr_encode_payloads*_device entries: the ciphertexts [first_ct, first_ct + n_ct) of

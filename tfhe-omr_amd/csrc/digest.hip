@@ -7,7 +7,7 @@
 // bitmap is enabled (omr_digest_enable_bitmap) folds each piece into the bitmap digest as well.
 // omr_digest_read_compact hands the digest out in compact form (compact.hpp) and leaves it as it is.
 // A session from omr_digest_begin_indexed holds no weight table: its payload encode computes the indexed
-// weights (common.hpp) in the kernel; one from omr_digest_begin_seek holds the seek of its board and the
+// weights (weights.hpp) in the kernel; one from omr_digest_begin_seek holds the seek of its board and the
 // kernel finds the reference's weights through it; everything else is shared.
 //
 // The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
@@ -148,11 +148,12 @@ omr_status digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index
     pw.combos = rp.combination_count;
     if (kind != PayloadWeights::TABLE) {
       pw.key = weight_key(weight_seed);
-      if (kind == PayloadWeights::SEEK) {
-        if (all > SEEK_MAX_DRAWS / ((uint64_t)rp.combination_count + 1))
-          return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": board too large");
-        OMR_TRY(omr_weight_seek_build_device(weight_seed, (uint64_t)rp.combination_count * all, &pw.seek, stream));
-      }
+      if (kind == PayloadWeights::SEEK)
+        OMR_TRY(resolve_seek(weight_seed, nullptr, rp.combination_count, all, who,
+                             [stream](const uint8_t *seed, uint64_t draws, omr_weight_seek *sk) {
+                               return omr_weight_seek_build_device(seed, draws, sk, stream);
+                             },
+                             &pw.seek));
     } else {
       std::vector<uint16_t> w((size_t)rp.cmb_cipher_count * rp.cmb_count_per_cipher * all);
       if ((s = omr_payload_weights(weight_seed, all, rp.combination_count, rp.cmb_cipher_count,

@@ -283,7 +283,7 @@ extern "C" omr_status omr_encode_payloads_seek(omr_ctx *c, const uint64_t *pv, c
 }
 
 // The device builder of a seek: weight_seek_scan_kernel over the raw words [0, draws + OMR_WEIGHT_SEEK_MAX] on
-// the current device, then the few hits sorted and turned into at[] on the host (common.hpp, seek_from_hits).
+// the current device, then the few hits sorted and turned into at[] on the host (weights.hpp, seek_from_hits).
 extern "C" omr_status omr_weight_seek_build_zone_device(const uint8_t seed[32], uint64_t draws, uint32_t zone,
                                                         omr_weight_seek *out, void *stream) {
   const char *who = "omr_weight_seek_build_device";

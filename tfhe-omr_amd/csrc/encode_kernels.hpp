@@ -7,6 +7,7 @@
 #include <climits>
 
 #include "kernels.hpp"
+#include "weights.hpp"
 
 namespace omr {
 
@@ -130,7 +131,7 @@ struct TableWeights {
   __device__ __forceinline__ uint32_t weight(int j, int i) const { return at[(size_t)j * all + i]; }
 };
 
-// Indexed weights (common.hpp, indexed_weight_block): no table. The ciphertext holds the combinations
+// Indexed weights (weights.hpp, indexed_weight_block): no table. The ciphertext holds the combinations
 // combo0 + j, j < per_ct; one at or beyond `combos` is padding with weight 0. Per round, thread
 // t < per_ct * nblk computes the one ChaCha12 block of (combination t / nblk, 16-message block t % nblk)
 // into LDS, nblk <= ENC_T / 16 + 1 being the 16-message blocks that the round's global indices touch.
@@ -163,7 +164,7 @@ struct IndexedWeights {  // its kernel reads wts itself (see there): no ROUND, n
   }
 };
 
-// The reference's weights found through a seek (common.hpp, "Reference payload weights by seek"): the same
+// The reference's weights found through a seek (weights.hpp, "Reference payload weights by seek"): the same
 // bits as TableWeights over omr_payload_weights' table. Row j of the board starts at draw j * all, so the
 // round's messages g0 .. g0 + cnt - 1 of combination j are the draws n0 = j * all + g0 onward, at the raw
 // positions pos(n0) .. pos(n0 + cnt - 1) <= pos(n0) + cnt - 1 + OMR_WEIGHT_SEEK_MAX: with the first one
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(ENC_T) void encode_payloads_seek_kernel(
 // The builders' scan (omr_weight_seek_build_device): one ChaCha12 block of the reference stream per thread
 // and grid-stride step, its 16 words compared with the zone. A rejected word at a raw position <= last takes
 // a slot of the list with one atomic; only the first SEEK_LIST slots exist, and the count says whether
-// the list is complete (common.hpp, SEEK_LIST). hits[0] is the count, hits[1 ..] the list.
+// the list is complete (weights.hpp, SEEK_LIST). hits[0] is the count, hits[1 ..] the list.
 constexpr int SEEK_SCAN_T = 256;
 __global__ __launch_bounds__(SEEK_SCAN_T) void weight_seek_scan_kernel(WeightKey key, uint64_t nblk, uint64_t last,
                                                                       uint32_t zone,

@@ -11,6 +11,7 @@
 #include "audit_decode.hpp"
 #include "auditor.hpp"
 #include "compact_math.hpp"
+#include "retrieve_system.hpp"
 #include "solve_kernels.hpp"
 
 using namespace omr;
@@ -166,68 +167,36 @@ omr_status indices_locked(omr_auditor *aud, const void *idx_cts, uint32_t n_ct, 
   OMR_TRY(decode_cts(aud, idx_cts, n_ct, bits, summary, who));
   std::vector<uint16_t> dec((size_t)n_ct * N2);
   if (n_ct) HIP_TRY(hipMemcpy(dec.data(), aud->ret.decoded, dec.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  const size_t spb = rp.slots_per_bucket, sps = rp.slots_per_segment;
   std::set<size_t> set;
   // decode_digest stops at the first ciphertext after which every pertinent index is known
   for (uint32_t c = 0; c < n_ct; ++c) {
-    const uint16_t *d = &dec[(size_t)c * N2];
-    for (size_t s0 = 0; s0 + sps <= (size_t)N2; s0 += sps)
-      for (size_t b0 = s0; b0 + spb <= s0 + sps; b0 += spb) {
-        if (d[b0 + spb - 1] != 1) continue;  // bucket marker
-        size_t v = 0;
-        for (size_t k = spb - 1; k-- > 0;) v = v * P + d[b0 + k];  // base-257 digits, LSD first
-        set.insert(v);
-      }
+    read_index_buckets(&dec[(size_t)c * N2], rp, set);
     if (set.size() == pertinent_count) break;
   }
-  *found = set.size();
-  size_t i = 0;
-  for (size_t v : set) {
-    if (i >= cap) break;
-    indices[i++] = v;
-  }
+  write_indices(set, indices, cap, found);
   return OMR_OK;
 }
 
-// Where the system's matrix comes from: the table's entries, the indexed weights of a seed, or the
-// reference's weights of a seed through a seek (seek NULL: built here, on the auditor's device).
-struct MatrixSource {
-  const uint16_t *weights = nullptr;
-  const uint8_t *weight_seed = nullptr;
-  bool by_seek = false;
-  const omr_weight_seek *seek = nullptr;
-};
-
-// retrieve_payloads_body's device twin after the NULL checks.
+// retrieve_payloads_body's device twin after the NULL test: the same system (retrieve_system.hpp), solved on
+// the device, so with a row cap; a NULL seek is built on the auditor's device.
 omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits, size_t all,
                            uint32_t combination_count, const MatrixSource &src, const size_t *indices,
                            size_t n_indices, uint16_t *payloads, omr_audit_summary *summary, const std::string &who) {
-  const uint16_t *weights = src.weights;
-  const uint8_t *weight_seed = src.weight_seed;
-  omr_retrieval_params rp;
-  OMR_TRY(omr_get_retrieval_params(all, n_indices, &rp));
-  const size_t rows = combination_count ? combination_count : rp.combination_count, cols = n_indices,
-               per = rp.cmb_count_per_cipher;
-  if (n_indices == 0) return OMR_OK;
-  if ((size_t)n_ct * per < rows) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": too few payload ciphertexts");
-  if (rows < cols) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": fewer combinations than indices");
-  for (size_t i = 0; i < n_indices; ++i)
-    if (indices[i] >= all) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": index out of range");
+  PayloadSystem sys;
+  OMR_TRY(payload_system(all, combination_count, n_ct, indices, n_indices, who, &sys));
+  if (sys.cols == 0) return OMR_OK;
+  const size_t rows = sys.rows, cols = sys.cols;
   if (rows > OMR_SOLVE_MAX_ROWS)
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": more than OMR_SOLVE_MAX_ROWS (8192) combinations");
   omr_auditor::Retrieve &r = aud->ret;
   hipStream_t st = aud->st;
   omr_weight_seek seek{};
-  if (src.by_seek) {
-    if (src.seek) {
-      if (!seek_covers(src.seek, rows, all))
-        return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": the seek does not cover combination_count * all draws");
-      seek = *src.seek;
-    } else {
-      if (all > SEEK_MAX_DRAWS / (rows + 1)) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": board too large");
-      OMR_TRY(omr_weight_seek_build_device(weight_seed, (uint64_t)rows * all, &seek, st));
-    }
-  }
+  if (src.by_seek)
+    OMR_TRY(resolve_seek(src.weight_seed, src.seek, rows, all, who,
+                         [st](const uint8_t *seed, uint64_t draws, omr_weight_seek *out) {
+                           return omr_weight_seek_build_device(seed, draws, out, st);
+                         },
+                         &seek));
   OMR_TRY(decode_cts(aud, pay_cts, n_ct, bits, summary, who.c_str()));
   // the stream is idle here (the decode ends with a synchronisation), so growing is safe
   HIP_TRY(r.matrix.reserve(rows * cols));
@@ -236,23 +205,24 @@ omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
   HIP_TRY(r.status.reserve(1));
   std::vector<uint16_t> h_m;
   std::vector<uint64_t> h_idx;
-  if (weights) {  // the table's entries, gathered on the host
+  if (src.weights) {  // the table's entries, gathered on the host
     h_m.resize(rows * cols);
-    for (size_t j = 0; j < rows; ++j)
-      for (size_t k = 0; k < cols; ++k) h_m[j * cols + k] = weights[j * all + indices[k]];
+    OMR_TRY(fill_matrix_host(src, seek, sys, all, indices, h_m.data()));
     HIP_TRY(hipMemcpyAsync(r.matrix, h_m.data(), h_m.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
   } else {
+    const WeightKey key = weight_key(src.weight_seed);
     h_idx.assign(indices, indices + cols);
     HIP_TRY(r.indices.reserve(cols));
     HIP_TRY(hipMemcpyAsync(r.indices, h_idx.data(), cols * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (src.by_seek)
-      retrieve_matrix_seek_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(weight_key(weight_seed), seek, all, r.indices,
-                                                                                 (uint32_t)rows, (uint32_t)cols, r.matrix);
+      retrieve_matrix_seek_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(key, seek, all, r.indices, (uint32_t)rows,
+                                                                                 (uint32_t)cols, r.matrix);
     else
-      retrieve_matrix_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(weight_key(weight_seed), r.indices, (uint32_t)rows,
-                                                                            (uint32_t)cols, r.matrix);
+      retrieve_matrix_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(key, r.indices, (uint32_t)rows, (uint32_t)cols,
+                                                                            r.matrix);
   }
-  retrieve_rhs_kernel<<<col_grid(rows * PAYLOAD_LEN), SOLVE_COL_T, 0, st>>>(r.decoded, (uint32_t)rows, (uint32_t)per, r.rhs);
+  retrieve_rhs_kernel<<<col_grid(rows * PAYLOAD_LEN), SOLVE_COL_T, 0, st>>>(r.decoded, (uint32_t)rows, (uint32_t)sys.per,
+                                                                            r.rhs);
   omr_status s = hipGetLastError() == hipSuccess ? OMR_OK : set_error(OMR_ERR_DEVICE, who + ": kernel launch failed");
   if (s == OMR_OK) s = launch_solve(aud, r.matrix, r.rhs, rows, cols, PAYLOAD_LEN, r.solution, r.status, st);
   uint32_t status = 0;
@@ -271,9 +241,24 @@ omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
   return OMR_OK;
 }
 
-omr_status check_bits(int bits, const std::string &who) {
+// The shared front of the entry points after their NULL test: bits, the auditor's lock, its device, then body().
+template <typename Body>
+omr_status with_auditor(omr_auditor *aud, int bits, const std::string &who, Body body) {
   if (bits && !compact_bits_ok(bits)) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": bits must be 0 or in [16, 32]");
-  return OMR_OK;
+  std::lock_guard<std::mutex> lk(aud->mu);
+  HIP_TRY(hipSetDevice(aud->device));
+  return body();
+}
+
+// The three omr_auditor_retrieve_payloads* entries: they differ in where the matrix comes from.
+omr_status auditor_payloads(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits, size_t all,
+                            uint32_t combination_count, const MatrixSource &src, const size_t *indices, size_t n_indices,
+                            uint16_t *payloads, const std::string &who) {
+  if (!retrieve_args_ok(aud, pay_cts, src, indices, n_indices, payloads))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
+  return with_auditor(aud, bits, who, [&] {
+    return payloads_locked(aud, pay_cts, n_ct, bits, all, combination_count, src, indices, n_indices, payloads, nullptr, who);
+  });
 }
 
 }  // namespace
@@ -284,54 +269,37 @@ extern "C" omr_status omr_auditor_retrieve_indices(omr_auditor *aud, const void 
   const char *who = "omr_auditor_retrieve_indices";
   if (!aud || !found || (n_ct && !idx_cts) || (cap && !indices))
     return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-  OMR_TRY(check_bits(bits, who));
-  omr_retrieval_params rp;
-  OMR_TRY(omr_get_retrieval_params(all_payloads_count, pertinent_count, &rp));
-  std::lock_guard<std::mutex> lk(aud->mu);
-  HIP_TRY(hipSetDevice(aud->device));
-  return indices_locked(aud, idx_cts, n_ct, bits, rp, pertinent_count, indices, cap, found, nullptr, who);
+  return with_auditor(aud, bits, who, [&] {
+    omr_retrieval_params rp;
+    OMR_TRY(omr_get_retrieval_params(all_payloads_count, pertinent_count, &rp));
+    return indices_locked(aud, idx_cts, n_ct, bits, rp, pertinent_count, indices, cap, found, nullptr, who);
+  });
 }
 
 extern "C" omr_status omr_auditor_retrieve_payloads(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
                                                     size_t all_payloads_count, uint32_t combination_count,
                                                     const uint16_t *weights, const size_t *indices, size_t n_indices,
                                                     uint16_t *payloads) {
-  const std::string who = "omr_auditor_retrieve_payloads";
-  if (!aud || !pay_cts || !weights || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
-  OMR_TRY(check_bits(bits, who));
-  std::lock_guard<std::mutex> lk(aud->mu);
-  HIP_TRY(hipSetDevice(aud->device));
-  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, MatrixSource{weights}, indices,
-                         n_indices, payloads, nullptr, who);
+  return auditor_payloads(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, MatrixSource{weights}, indices,
+                          n_indices, payloads, "omr_auditor_retrieve_payloads");
 }
 
 extern "C" omr_status omr_auditor_retrieve_payloads_indexed(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
                                                             size_t all_payloads_count, uint32_t combination_count,
                                                             const uint8_t weight_seed[32], const size_t *indices,
                                                             size_t n_indices, uint16_t *payloads) {
-  const std::string who = "omr_auditor_retrieve_payloads_indexed";
-  if (!aud || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
-  OMR_TRY(check_bits(bits, who));
-  std::lock_guard<std::mutex> lk(aud->mu);
-  HIP_TRY(hipSetDevice(aud->device));
-  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count, MatrixSource{nullptr, weight_seed},
-                         indices, n_indices, payloads, nullptr, who);
+  return auditor_payloads(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count,
+                          MatrixSource{nullptr, weight_seed}, indices, n_indices, payloads,
+                          "omr_auditor_retrieve_payloads_indexed");
 }
 
 extern "C" omr_status omr_auditor_retrieve_payloads_seek(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
                                                          size_t all_payloads_count, uint32_t combination_count,
                                                          const uint8_t weight_seed[32], const omr_weight_seek *seek,
                                                          const size_t *indices, size_t n_indices, uint16_t *payloads) {
-  const std::string who = "omr_auditor_retrieve_payloads_seek";
-  if (!aud || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
-  OMR_TRY(check_bits(bits, who));
-  std::lock_guard<std::mutex> lk(aud->mu);
-  HIP_TRY(hipSetDevice(aud->device));
-  return payloads_locked(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count,
-                         MatrixSource{nullptr, weight_seed, true, seek}, indices, n_indices, payloads, nullptr, who);
+  return auditor_payloads(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count,
+                          MatrixSource{nullptr, weight_seed, true, seek}, indices, n_indices, payloads,
+                          "omr_auditor_retrieve_payloads_seek");
 }
 
 extern "C" omr_status omr_auditor_decode_digest_indexed(omr_auditor *aud, const void *idx_cts, uint32_t n_idx_ct,
@@ -342,17 +310,16 @@ extern "C" omr_status omr_auditor_decode_digest_indexed(omr_auditor *aud, const 
   const std::string who = "omr_auditor_decode_digest_indexed";
   if (!aud || !found || !pay_cts || !weight_seed || (n_idx_ct && !idx_cts) || (cap && (!indices || !payloads)))
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
-  OMR_TRY(check_bits(bits, who));
-  omr_retrieval_params rp;
-  OMR_TRY(omr_get_retrieval_params(all_payloads_count, pertinent_count, &rp));
-  std::lock_guard<std::mutex> lk(aud->mu);
-  HIP_TRY(hipSetDevice(aud->device));
-  omr_audit_summary sum{};  // merged into the caller's only when the whole call succeeds
-  OMR_TRY(indices_locked(aud, idx_cts, n_idx_ct, bits, rp, pertinent_count, indices, cap, found, summary ? &sum : nullptr,
-                         who.c_str()));
-  if (cap < *found) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": more indices found than cap");
-  OMR_TRY(payloads_locked(aud, pay_cts, n_pay_ct, bits, all_payloads_count, rp.combination_count,
-                          MatrixSource{nullptr, weight_seed}, indices, *found, payloads, summary ? &sum : nullptr, who));
-  if (summary) merge_summary(*summary, sum);
-  return OMR_OK;
+  return with_auditor(aud, bits, who, [&] {
+    omr_retrieval_params rp;
+    OMR_TRY(omr_get_retrieval_params(all_payloads_count, pertinent_count, &rp));
+    omr_audit_summary sum{};  // merged into the caller's only when the whole call succeeds
+    OMR_TRY(indices_locked(aud, idx_cts, n_idx_ct, bits, rp, pertinent_count, indices, cap, found,
+                           summary ? &sum : nullptr, who.c_str()));
+    if (cap < *found) return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": more indices found than cap");
+    OMR_TRY(payloads_locked(aud, pay_cts, n_pay_ct, bits, all_payloads_count, rp.combination_count,
+                            MatrixSource{nullptr, weight_seed}, indices, *found, payloads, summary ? &sum : nullptr, who));
+    if (summary) merge_summary(*summary, sum);
+    return OMR_OK;
+  });
 }

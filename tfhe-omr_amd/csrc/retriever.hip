@@ -12,6 +12,7 @@
 
 #include "audit_decode.hpp"
 #include "host_ring.hpp"
+#include "retrieve_system.hpp"
 
 using namespace omr;
 
@@ -100,29 +101,16 @@ extern "C" omr_status omr_retrieve_indices(const omr_secret_key_pack *sk, const 
   if (!sk || !found || (n_ct && !idx_cts) || (cap && !indices))
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_indices: NULL argument");
   omr_retrieval_params rp;
-  omr_status st = omr_get_retrieval_params(all_payloads_count, pertinent_count, &rp);
-  if (st != OMR_OK) return st;
-  const size_t spb = rp.slots_per_bucket, sps = rp.slots_per_segment;
+  OMR_TRY(omr_get_retrieval_params(all_payloads_count, pertinent_count, &rp));
   std::set<size_t> set;
   std::vector<uint32_t> dec(N2);
   // decode_digest stops at the first ciphertext after which every pertinent index is known
   for (uint32_t c = 0; c < n_ct; ++c) {
     decrypt_decode_one(sk, idx_cts + (size_t)c * 2 * N2, P, dec.data());
-    for (size_t s0 = 0; s0 + sps <= (size_t)N2; s0 += sps)
-      for (size_t b0 = s0; b0 + spb <= s0 + sps; b0 += spb) {
-        if (dec[b0 + spb - 1] != 1) continue;  // bucket marker
-        size_t v = 0;
-        for (size_t k = spb - 1; k-- > 0;) v = v * P + dec[b0 + k];  // base-257 digits, LSD first
-        set.insert(v);
-      }
+    read_index_buckets(dec.data(), rp, set);
     if (set.size() == pertinent_count) break;
   }
-  *found = set.size();
-  size_t i = 0;
-  for (size_t v : set) {
-    if (i >= cap) break;
-    indices[i++] = v;
-  }
+  write_indices(set, indices, cap, found);
   return OMR_OK;
 }
 
@@ -184,38 +172,34 @@ omr_status solve_mod257(const uint16_t *matrix, const uint16_t *rhs, size_t rows
   return OMR_OK;
 }
 
-// The body of omr_retrieve_payloads and omr_retrieve_payloads_indexed after their NULL checks: they
-// differ in where the system's matrix comes from. fill(rows, m) writes m[j][k], the weight of combination
-// j for the k-th index, and returns a status.
-template <typename Fill>
-omr_status retrieve_payloads_body(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
-                                  size_t all_payloads_count, uint32_t combination_count, const size_t *indices,
-                                  size_t n_indices, uint16_t *payloads, const std::string &who, Fill fill) {
-  omr_retrieval_params rp;
-  omr_status st = omr_get_retrieval_params(all_payloads_count, n_indices, &rp);
-  if (st != OMR_OK) return st;
-  const size_t rows = combination_count ? combination_count : rp.combination_count, cols = n_indices,
-               per = rp.cmb_count_per_cipher;
-  if (n_indices == 0) return OMR_OK;
-  if ((size_t)n_ct * per < rows)
-    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": too few payload ciphertexts");
-  if (rows < cols)  // matrix.rs:171 asserts num_rows >= num_cols
-    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": fewer combinations than indices");
-  for (size_t i = 0; i < n_indices; ++i)
-    if (indices[i] >= all_payloads_count)
-      return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": index out of range");
+// The body of the three omr_retrieve_payloads* entries after their NULL test: they differ in where the
+// system's matrix comes from (retrieve_system.hpp). No row cap: the solve is this file's, on this thread.
+omr_status retrieve_payloads_body(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct, size_t all,
+                                  uint32_t combination_count, const MatrixSource &src, const size_t *indices,
+                                  size_t n_indices, uint16_t *payloads, const std::string &who) {
+  if (!retrieve_args_ok(sk, pay_cts, src, indices, n_indices, payloads))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
+  PayloadSystem sys;
+  OMR_TRY(payload_system(all, combination_count, n_ct, indices, n_indices, who, &sys));
+  if (sys.cols == 0) return OMR_OK;
+  omr_weight_seek seek{};
+  if (src.by_seek)
+    OMR_TRY(resolve_seek(src.weight_seed, src.seek, sys.rows, all, who,
+                         [](const uint8_t *seed, uint64_t draws, omr_weight_seek *out) {
+                           return omr_weight_seek_build_cpu(seed, draws, 0, out);
+                         },
+                         &seek));
   // decode_combined_payloads: combination j lives in ciphertext j / per, slots (j % per) * 612..
-  std::vector<uint16_t> rhs(rows * PAYLOAD_LEN);
+  std::vector<uint16_t> rhs(sys.rows * PAYLOAD_LEN);
   std::vector<uint32_t> dec((size_t)n_ct * N2);
   parallel_for(n_ct, 0, [&](size_t c) { decrypt_decode_one(sk, pay_cts + c * 2 * N2, P, &dec[c * N2]); });
-  for (size_t j = 0; j < rows; ++j)
+  for (size_t j = 0; j < sys.rows; ++j)
     for (int b = 0; b < PAYLOAD_LEN; ++b)
-      rhs[j * PAYLOAD_LEN + b] = (uint16_t)dec[(j / per) * N2 + (j % per) * PAYLOAD_LEN + b];
-  // matrix[j][k] = weight of combination j for the k-th retrieved index (retriever.rs:220-238)
-  std::vector<uint16_t> m(rows * cols);
-  if ((st = fill(rows, m.data())) != OMR_OK) return st;
+      rhs[j * PAYLOAD_LEN + b] = (uint16_t)dec[(j / sys.per) * N2 + (j % sys.per) * PAYLOAD_LEN + b];
+  std::vector<uint16_t> m(sys.rows * sys.cols);
+  OMR_TRY(fill_matrix_host(src, seek, sys, all, indices, m.data()));
   // forward elimination with the first non-zero pivot, then back substitution (matrix.rs), on this thread
-  return solve_mod257(m.data(), rhs.data(), rows, cols, PAYLOAD_LEN, payloads, nullptr, 1);
+  return solve_mod257(m.data(), rhs.data(), sys.rows, sys.cols, PAYLOAD_LEN, payloads, nullptr, 1);
 }
 
 }  // namespace
@@ -225,29 +209,26 @@ extern "C" omr_status omr_retrieve_payloads(const omr_secret_key_pack *sk, const
                                             uint32_t combination_count, const uint16_t *weights,
                                             const size_t *indices,
                                             size_t n_indices, uint16_t *payloads) {
-  if (!sk || !pay_cts || !weights || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads: NULL argument");
-  return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
-                                "omr_retrieve_payloads", [&](size_t rows, uint16_t *m) {
-                                  for (size_t j = 0; j < rows; ++j)
-                                    for (size_t k = 0; k < n_indices; ++k)
-                                      m[j * n_indices + k] = weights[j * all_payloads_count + indices[k]];
-                                  return OMR_OK;
-                                });
+  return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count, MatrixSource{weights}, indices,
+                                n_indices, payloads, "omr_retrieve_payloads");
 }
 
 extern "C" omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *sk, const uint64_t *pay_cts,
                                                     uint32_t n_ct, size_t all_payloads_count,
                                                     uint32_t combination_count, const uint8_t weight_seed[32],
                                                     const size_t *indices, size_t n_indices, uint16_t *payloads) {
-  if (!sk || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_indexed: NULL argument");
-  return retrieve_payloads_body(
-      sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
-      "omr_retrieve_payloads_indexed", [&](size_t rows, uint16_t *m) {
-        // every row is a real combination of the board: rows = combination_count (or its default)
-        return omr_indexed_weights_at(weight_seed, (uint32_t)rows, 0, (uint32_t)rows, indices, n_indices, m, 0);
-      });
+  return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count,
+                                MatrixSource{nullptr, weight_seed}, indices, n_indices, payloads,
+                                "omr_retrieve_payloads_indexed");
+}
+
+extern "C" omr_status omr_retrieve_payloads_seek(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
+                                                 size_t all_payloads_count, uint32_t combination_count,
+                                                 const uint8_t weight_seed[32], const omr_weight_seek *seek,
+                                                 const size_t *indices, size_t n_indices, uint16_t *payloads) {
+  return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count,
+                                MatrixSource{nullptr, weight_seed, true, seek}, indices, n_indices, payloads,
+                                "omr_retrieve_payloads_seek");
 }
 
 extern "C" omr_status omr_solve_mod257_cpu(const uint16_t *matrix, const uint16_t *rhs, size_t rows, size_t cols,
@@ -262,28 +243,6 @@ extern "C" omr_status omr_solve_mod257_cpu(const uint16_t *matrix, const uint16_
   } catch (const std::bad_alloc &) {
     return set_error(OMR_ERR_OUT_OF_MEMORY, "omr_solve_mod257_cpu: host allocation failed");
   }
-}
-
-extern "C" omr_status omr_retrieve_payloads_seek(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
-                                                 size_t all_payloads_count, uint32_t combination_count,
-                                                 const uint8_t weight_seed[32], const omr_weight_seek *seek,
-                                                 const size_t *indices, size_t n_indices, uint16_t *payloads) {
-  if (!sk || !pay_cts || !weight_seed || (n_indices && (!indices || !payloads)))
-    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_seek: NULL argument");
-  return retrieve_payloads_body(
-      sk, pay_cts, n_ct, all_payloads_count, combination_count, indices, n_indices, payloads,
-      "omr_retrieve_payloads_seek", [&](size_t rows, uint16_t *m) {
-        // every row is a real combination of the board: rows = combination_count (or its default)
-        omr_weight_seek built;
-        if (!seek) {
-          if (all_payloads_count > SEEK_MAX_DRAWS / (rows + 1))
-            return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_retrieve_payloads_seek: board too large");
-          const omr_status b = omr_weight_seek_build_cpu(weight_seed, (uint64_t)rows * all_payloads_count, 0, &built);
-          if (b != OMR_OK) return b;
-        }
-        return omr_payload_weights_at(weight_seed, all_payloads_count, (uint32_t)rows, seek ? seek : &built, 0,
-                                      (uint32_t)rows, indices, n_indices, m, 0);
-      });
 }
 
 extern "C" omr_status omr_bitmap_ct_count(size_t all, uint32_t *n_ct) {

@@ -22,6 +22,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "weights.hpp"
 
 namespace omr {
 
@@ -281,7 +282,7 @@ solve_store_kernel(const uint16_t *__restrict__ W, uint32_t ld, uint32_t cols, u
   solution[idx] = W[(idx / width) * ld + cols + idx % width];
 }
 
-// The indexed matrix of a retrieval: m[j][k] = w(j, indices[k]) (common.hpp, indexed_weight_block); one
+// The indexed matrix of a retrieval: m[j][k] = w(j, indices[k]) (weights.hpp, indexed_weight_block); one
 // thread per (combination, index). Every row is a real combination of the board.
 __global__ void __launch_bounds__(SOLVE_COL_T)
 retrieve_matrix_kernel(WeightKey key, const uint64_t *__restrict__ indices, uint32_t rows, uint32_t cols,
@@ -297,7 +298,7 @@ retrieve_matrix_kernel(WeightKey key, const uint64_t *__restrict__ indices, uint
   m[idx] = v;
 }
 
-// The same matrix in the reference's convention (common.hpp, "Reference payload weights by seek"):
+// The same matrix in the reference's convention (weights.hpp, "Reference payload weights by seek"):
 // m[j][k] = w(j * all + indices[k]), the word at raw position pos(n) of the reference stream.
 __global__ void __launch_bounds__(SOLVE_COL_T)
 retrieve_matrix_seek_kernel(WeightKey key, omr_weight_seek seek, uint64_t all, const uint64_t *__restrict__ indices,
