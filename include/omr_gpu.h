@@ -441,7 +441,10 @@ omr_status omr_detect_with_time_info(omr_ctx *ctx, const uint16_t *clue_a, const
  * messages with global indices [global_offset, global_offset+D) of an all_payloads_count board.
  * Buckets come from a seeded counter-based stream (the reference uses thread_rng, :262) so
  * that shards agree. out u64 [2][2048] (NTT domain), a partial digest summed mod q2 across
- * shards. */
+ * shards. The device entry returns OMR_ERR_INVALID_ARGUMENT before anything is enqueued for n_ct = 0
+ * or n_ct > 65,535, a range [global_offset, global_offset + D) that does not lie on the board
+ * (checked without the sum, which may wrap), D > INT32_MAX, or a NULL d_pv with D > 0; the host entry
+ * inherits the checks. */
 omr_status omr_encode_indices(omr_ctx *ctx, const uint64_t *pv, size_t D, size_t global_offset,
                               size_t all_payloads_count, uint64_t seed, uint32_t ct,
                               uint64_t *out);

@@ -566,7 +566,7 @@ void oref_get_retrieval_params(size_t all, size_t pertinent, oref_retrieval_para
   const uint64_t p = OREF_P;
   uint32_t pw = 0;
   uint64_t acc = 1;
-  while (acc * p <= all) { acc *= p; pw++; } /* ilog(all, p) */
+  while (acc <= all / p) { acc *= p; pw++; } /* ilog(all, p): acc * p <= all, and no product to wrap */
   if (acc < all) pw++;                        /* p^pow < all -> pow += 1 */
   if (pw == 0) pw = 1;
   rp->index_slots_per_bucket = pw;

@@ -133,6 +133,32 @@ def test_level2_mac_four_products_per_reduction():
     assert (0.5 + 5 * prod) * Q2 > 2.0**53
 
 
+def test_encode_fold_bound():
+    """encode_kernels.hpp encode_fold: WgNtt<Mod<2>, 128, 16>::fwd from the slots (|x| <= 128: centred
+    residues mod 257), then acc = red(acc + mm(from_u64(pv), x)) with x as the transform leaves it.
+    RED_FWD = 6: stages 0..5, one reduction of every element, stages 6..10. Either run of stages ends below
+    4.82q (six stages from nothing and five from q/2 give the same 4.811q), so |mm(pv, x)| <= 1.41q with |pv| <= (q - 1) / 2,
+    and a reduced accumulator (|acc| <= q/2 + 2) plus the product stays below 1.91q < 2^53 = 8q. mm is
+    symmetric in its operands (the rounded product and its fma remainder are), so _mm_bound and _replay_mm
+    hold with the large operand second, as the fold has it."""
+    q = Q2
+    red = 0.5 + 2 / q
+    b = 128 / q
+    for _ in range(6):  # stages 0..5
+        b = _stage(b, b)
+    assert 4.81 < b < 4.82  # what the reduction takes; the largest mm operand so far is stage 5's 3.64q
+    b = red
+    for _ in range(5):  # stages 6..10
+        b = _stage(b, b)
+    assert 4.81 < b < 4.82  # the output bound
+    prod = _mm_bound(b)
+    assert 1.40 < prod < 1.41
+    assert 1.90 < red + prod < 1.91 and (red + prod) * q < 2.0**53
+    # from_u64 with `>=` in place of `>` would hand mm (q + 1) / 2: the same bound to the figures given
+    assert _mm_bound(b) * (1 + 2 / q) < 1.41
+    _replay_mm(4.82, 16)
+
+
 def test_inverse_twiddles_mirror_forward_table():
     """device_ntt.hpp inv_passC<MIRROR>: psi^-brv(2^s + j) = -psi^brv(2^(s+1) - 1 - j) (mod q2) for
     every node of the 2048-point negacyclic table (psi = 22^((q2-1)/4096), 11-bit reversal), so

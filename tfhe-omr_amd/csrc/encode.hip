@@ -174,7 +174,9 @@ extern "C" omr_status omr_encode_indices_device(omr_ctx *c, const uint64_t *pv, 
                                                 size_t offset, size_t all, uint64_t seed,
                                                 uint32_t first_ct, uint32_t n_ct, uint64_t *out,
                                                 void *stream) {
-  if (!c || !out || (D && !pv) || n_ct == 0 || offset + D > all || D > (size_t)INT32_MAX)
+  // n_ct is the grid's y extent, D the kernel's int
+  if (!c || !out || (D && !pv) || n_ct == 0 || n_ct > 65535 || !range_on_board(offset, D, all) ||
+      D > (size_t)INT32_MAX)
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_indices_device: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));

@@ -18,7 +18,9 @@ extern "C" omr_status omr_get_retrieval_params(size_t all, size_t pertinent,
   if (!rp || all == 0) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_get_retrieval_params");
   uint32_t pw = 0;
   uint64_t acc = 1;
-  while (acc * (uint64_t)P <= all) {
+  // acc * p <= all without the product: 257^7 * 257 wraps to 257^8 - 2^64 = 5.8e17, and a board of that size or
+  // more counted a ninth digit and on (for the largest size_t the loop never ended)
+  while (acc <= all / (uint64_t)P) {
     acc *= (uint64_t)P;
     ++pw;
   }
