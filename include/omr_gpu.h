@@ -96,6 +96,76 @@ omr_status omr_keygen_detection_key_device(const omr_secret_key_pack *sk, uint64
                                            uint64_t *d_trace_key, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sender — SecretKeyPack::generate_clue_key (key_gen/secret.rs:99-107), Sender::new(clue_key, 7) and
+ * Sender::gen_clues (sender.rs:27-32, key_gen/clue.rs:27-34), and the recipient's
+ * SecretKeyPack::decrypt_clue (secret.rs:267-270). A sender holds public clue keys only; the generators
+ * above take the recipient's pack and stay as they are.
+ *
+ * Generation. The clue of message m of a call is LwePublicKeyRlweMode::encrypt_multi_messages(&[0;7])
+ * under key recipient[m]: u = A r + e1, v = B r + e2 over Z_2048[X]/(X^512 + 1), clue = (u, v[0..7]). Its
+ * randomness is Stream(seed, DOM_CLUE = 20, first + m), the stream omr_gen_clues uses: r (16 words, bit b
+ * of word k is r[32 k + b]), then the 512 Gaussians of e1, then the 7 of e2. So a sender over the one key
+ * omr_secret_clue_key(sk) returns the bits of omr_gen_clues(sk, ..). The clue of a global index does not
+ * depend on the range it is generated in, on the other messages' recipients or on nthreads. count = 0
+ * does nothing. On the CPU an id >= n_keys returns OMR_ERR_INVALID_ARGUMENT before anything is written.
+ * The device entry returns after the stream has finished the work, as omr_gen_clues_device does; if an
+ * id was out of range it returns OMR_ERR_INVALID_ARGUMENT naming the smallest offending message index of
+ * the call, that message's clue (and that of every other offending message) is not written, all other
+ * clues are written, and the sender stays usable.
+ *
+ * Opening. Clue words are reduced mod 2048 first. For clue i of a message, phase_i = b_i - <a^(i), s0>
+ * mod 2048 with a^(i) the extraction of detector.rs:514 (a^(i)[j] = a[i - j] for j <= i, -a[512 + i - j]
+ * otherwise), value_i = ((8 phase_i + 1024) >> 11) & 7, noise_i = phase_i - 256 value_i centred into
+ * [-128, 127], pertinent = (all seven value_i == 0), the window the first-level LUT accepts, and
+ * max_abs_noise = max_i |noise_i|.
+ * ------------------------------------------------------------------------------------- */
+/* LwePublicKeyRlweMode (A, B = A s0 + E) over Z_2048[X]/(X^512 + 1): 2,048 bytes, the wire form */
+typedef struct {
+  uint16_t a[512];
+  uint16_t b[512];
+} omr_clue_key;
+
+omr_status omr_secret_clue_key(const omr_secret_key_pack *sk, omr_clue_key *out);
+/* The words >= 2048 over n_keys keys; reports, does not reject. */
+omr_status omr_clue_key_validate(const omr_clue_key *keys, size_t n_keys, uint64_t *noncanonical);
+/* K: the largest |e| the generators' sampler can draw for a clue key or a clue (the last index of its
+ * cumulative table, csrc/rng.hpp). */
+omr_status omr_clue_key_noise_support(uint64_t *K);
+/* The key's noise e = B - A s0 mod 2048, centred into [-1024, 1023]; words are reduced mod 2048 first and
+ * a word >= 2048 counts as non-canonical; coeffs_over counts the coefficients with |e| > limit
+ * (UINT64_MAX = K). Any output may be NULL. CPU. */
+omr_status omr_clue_key_audit(const omr_secret_key_pack *sk, const omr_clue_key *key, uint64_t limit,
+                              uint64_t *max_abs_noise, uint32_t *coeffs_over, uint32_t *noncanonical);
+
+typedef struct omr_sender omr_sender;
+/* Copies the table of n_keys keys. device >= 0 also uploads it, the Gaussian table and the error word to
+ * that device, once; device < 0: CPU only (omr_sender_gen_clues_device then returns
+ * OMR_ERR_INVALID_ARGUMENT). OMR_ERR_INVALID_ARGUMENT for n_keys = 0, n_keys > UINT32_MAX, or a word
+ * >= 2048 (the message names the first such key). Calls on one sender are serialised. */
+omr_status omr_sender_create(const omr_clue_key *keys, size_t n_keys, int device, omr_sender **out);
+void       omr_sender_destroy(omr_sender *s);
+/* The clue of global index first + m under key recipient[m] (recipient NULL: key 0 for every message):
+ * clue_a u16 [count][512], clue_b u16 [count][7]. nthreads <= 0: the host's cores, at most 16. */
+omr_status omr_sender_gen_clues(const omr_sender *s, const uint32_t *recipient, uint64_t seed, uint64_t first,
+                                size_t count, uint16_t *clue_a, uint16_t *clue_b, int nthreads);
+/* The same bits into device buffers of the sender's device on hip_stream (NULL = null stream);
+ * d_recipient u32 [count] in device memory, or NULL. */
+omr_status omr_sender_gen_clues_device(omr_sender *s, const uint32_t *d_recipient, uint64_t seed,
+                                       uint64_t first, size_t count, uint16_t *d_clue_a, uint16_t *d_clue_b,
+                                       void *hip_stream);
+
+/* decrypt_clue for all 7 clues of each of count messages: values u8 [count][7], pertinent u8 [count],
+ * max_abs_noise u8 [count]; any output may be NULL, not all three. count = 0 does nothing. */
+omr_status omr_clue_open(const omr_secret_key_pack *sk, const uint16_t *clue_a, const uint16_t *clue_b,
+                         size_t count, uint8_t *values, uint8_t *pertinent, uint8_t *max_abs_noise,
+                         int nthreads);
+/* The same on device buffers of the current HIP device (d_clue_a 16-byte aligned) on hip_stream; the
+ * call hands s0 to the kernel itself and returns after the stream has finished the work. */
+omr_status omr_clue_open_device(const omr_secret_key_pack *sk, const uint16_t *d_clue_a,
+                                const uint16_t *d_clue_b, size_t count, uint8_t *d_values,
+                                uint8_t *d_pertinent, uint8_t *d_max_abs_noise, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------
  * Seeded detection key (none in the reference): the form a recipient sends and a server stores.
  * More than half of a detection key is uniform masks that carry no secret (the `a` half of every
  * RLWE row, 670 of the 671 words of every key-switching row). A seeded key carries a public 64-bit

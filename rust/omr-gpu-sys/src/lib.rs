@@ -68,6 +68,17 @@ pub mod ffi {
     pub struct OmrAuditor {
         _private: [u8; 0],
     }
+    #[repr(C)]
+    pub struct OmrSender {
+        _private: [u8; 0],
+    }
+    /// `omr_clue_key`: LwePublicKeyRlweMode (A, B = A s0 + E) over Z_2048[X]/(X^512 + 1), the wire form.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, PartialEq, Eq)]
+    pub struct OmrClueKey {
+        pub a: [u16; OMR_N0],
+        pub b: [u16; OMR_N0],
+    }
     pub const OMR_AUDIT_RESIDUAL_BINS: usize = 50;
     /// `omr_ct_audit`: the record that classifies one ciphertext.
     #[repr(C)]
@@ -213,6 +224,26 @@ pub mod ffi {
         pub fn omr_keygen_detection_key_device(sk: *const OmrSecretKeyPack, seed: u64, d_bsk1: *mut u32,
                                                d_ksk: *mut u32, d_bsk2: *mut u64, d_trace_key: *mut u64,
                                                stream: *mut c_void) -> OmrStatus;
+
+        // sender: public clue keys, mixed-recipient clues, clue opening (sender.rs:27-32, secret.rs:99-107, :267-270)
+        pub fn omr_secret_clue_key(sk: *const OmrSecretKeyPack, out: *mut OmrClueKey) -> OmrStatus;
+        pub fn omr_clue_key_validate(keys: *const OmrClueKey, n_keys: usize, noncanonical: *mut u64) -> OmrStatus;
+        pub fn omr_clue_key_noise_support(k: *mut u64) -> OmrStatus;
+        pub fn omr_clue_key_audit(sk: *const OmrSecretKeyPack, key: *const OmrClueKey, limit: u64,
+                                  max_abs_noise: *mut u64, coeffs_over: *mut u32, noncanonical: *mut u32) -> OmrStatus;
+        pub fn omr_sender_create(keys: *const OmrClueKey, n_keys: usize, device: c_int,
+                                 out: *mut *mut OmrSender) -> OmrStatus;
+        pub fn omr_sender_destroy(s: *mut OmrSender);
+        pub fn omr_sender_gen_clues(s: *const OmrSender, recipient: *const u32, seed: u64, first: u64, count: usize,
+                                    clue_a: *mut u16, clue_b: *mut u16, nthreads: c_int) -> OmrStatus;
+        pub fn omr_sender_gen_clues_device(s: *mut OmrSender, d_recipient: *const u32, seed: u64, first: u64,
+                                           count: usize, d_clue_a: *mut u16, d_clue_b: *mut u16,
+                                           hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_clue_open(sk: *const OmrSecretKeyPack, clue_a: *const u16, clue_b: *const u16, count: usize,
+                             values: *mut u8, pertinent: *mut u8, max_abs_noise: *mut u8, nthreads: c_int) -> OmrStatus;
+        pub fn omr_clue_open_device(sk: *const OmrSecretKeyPack, d_clue_a: *const u16, d_clue_b: *const u16,
+                                    count: usize, d_values: *mut u8, d_pertinent: *mut u8, d_max_abs_noise: *mut u8,
+                                    hip_stream: *mut c_void) -> OmrStatus;
 
         // seeded detection key: the bodies of a key whose masks come from a public seed
         pub fn omr_keygen_seeded_key(sk: *const OmrSecretKeyPack, seed: u64, mask_seed: u64, bsk1_b: *mut u32,
@@ -731,6 +762,72 @@ impl SecretKeyPack {
 impl Drop for SecretKeyPack {
     fn drop(&mut self) {
         unsafe { omr_secret_destroy(self.raw) }
+    }
+}
+
+/// `ClueKey` (key_gen/clue.rs): the public key a sender needs, 2,048 bytes.
+pub type ClueKey = OmrClueKey;
+
+impl SecretKeyPack {
+    /// `SecretKeyPack::generate_clue_key` (secret.rs:99-107).
+    pub fn generate_clue_key(&self) -> Result<ClueKey, OmrError> {
+        let mut k = ClueKey { a: [0; OMR_N0], b: [0; OMR_N0] };
+        check(unsafe { omr_secret_clue_key(self.raw, &mut k) })?;
+        Ok(k)
+    }
+    /// `SecretKeyPack::decrypt_clue` (secret.rs:267-270) for every clue of every message: whether the message
+    /// is pertinent (all seven values zero), per message.
+    pub fn open_clues(&self, clues: &[Clue]) -> Result<Vec<bool>, OmrError> {
+        let a: Vec<u16> = clues.iter().flat_map(|c| c.a.iter().copied()).collect();
+        let b: Vec<u16> = clues.iter().flat_map(|c| c.b.iter().copied()).collect();
+        let mut p = vec![0u8; clues.len()];
+        check(unsafe {
+            omr_clue_open(self.raw, a.as_ptr(), b.as_ptr(), clues.len(), std::ptr::null_mut(), p.as_mut_ptr(),
+                          std::ptr::null_mut(), 0)
+        })?;
+        Ok(p.into_iter().map(|x| x != 0).collect())
+    }
+}
+
+/// `Sender` (sender.rs:27-32) over a table of clue keys: message `m` of a call is addressed to key
+/// `recipient[m]`. CPU entry; a sender created with a device also serves `omr_sender_gen_clues_device`.
+pub struct Sender {
+    raw: *mut OmrSender,
+}
+unsafe impl Send for Sender {}
+
+impl Sender {
+    /// `Sender::new(clue_key, 7)` for one or more recipients; `device` None: CPU only.
+    pub fn new(keys: &[ClueKey], device: Option<i32>) -> Result<Self, OmrError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { omr_sender_create(keys.as_ptr(), keys.len(), device.unwrap_or(-1), &mut raw) })?;
+        Ok(Self { raw })
+    }
+    /// `Sender::gen_clues` for global message indices `first..first + recipient.len()`.
+    pub fn gen_clues(&self, recipient: &[u32], seed: u64, first: u64) -> Result<Vec<Clue>, OmrError> {
+        let count = recipient.len();
+        let mut a = vec![0u16; count * OMR_N0];
+        let mut b = vec![0u16; count * OMR_CLUE_COUNT];
+        check(unsafe {
+            omr_sender_gen_clues(self.raw, recipient.as_ptr(), seed, first, count, a.as_mut_ptr(), b.as_mut_ptr(), 0)
+        })?;
+        Ok((0..count)
+            .map(|m| {
+                let mut c = Clue { a: [0; OMR_N0], b: [0; OMR_CLUE_COUNT] };
+                c.a.copy_from_slice(&a[m * OMR_N0..(m + 1) * OMR_N0]);
+                c.b.copy_from_slice(&b[m * OMR_CLUE_COUNT..(m + 1) * OMR_CLUE_COUNT]);
+                c
+            })
+            .collect())
+    }
+    pub fn raw(&self) -> *mut OmrSender {
+        self.raw
+    }
+}
+
+impl Drop for Sender {
+    fn drop(&mut self) {
+        unsafe { omr_sender_destroy(self.raw) }
     }
 }
 

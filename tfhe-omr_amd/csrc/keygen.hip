@@ -1,5 +1,6 @@
-// Host-side key generation and clue generation (CPU), and the library's error text. The payload
-// weights and the digest layout are in weights.hip.
+// Host-side key generation and clue generation (CPU), the sender over public clue keys with the
+// recipient's clue opening and clue-key audit, and the library's error text. The payload weights and the
+// digest layout are in weights.hip.
 //
 // Mirrors omr_core's KeyGen / SecretKeyPack / Sender (key_gen/mod.rs:16-27,
 // key_gen/secret.rs:46-209, key_gen/clue.rs:27-34, sender.rs:27-32). Every random draw comes
@@ -16,6 +17,7 @@
 
 #include "host_ring.hpp"
 #include "rng.hpp"
+#include "sender.hpp"
 
 namespace omr {
 
@@ -277,7 +279,52 @@ extern "C" omr_status omr_key_masks(uint64_t mask_seed, int component, size_t fi
 }
 
 // Sender::gen_clues: ClueKey::gen_clues -> LwePublicKeyRlweMode::encrypt_multi_messages(&[0;7]).
-// u = A*r + e1, v = B*r + e2 (+ Delta*m = 0), r binary; clue = (u, v[0..7]).
+// u = A*r + e1, v = B*r + e2 (+ Delta*m = 0), r binary; clue = (u, v[0..7]). One body over a key (A, B)
+// for the pack's own key (omr_gen_clues) and a sender's table (omr_sender_gen_clues): the clue of global
+// message index g from Stream(seed, DOM_CLUE, g).
+namespace omr {
+namespace {
+void clue_body(const uint16_t *A, const uint16_t *B, const Gaussian &g, uint64_t seed, uint64_t index, uint16_t *ca,
+               uint16_t *cb) {
+  Stream st(seed, DOM_CLUE, index);
+  uint8_t r[N0];
+  for (int w = 0; w < N0 / 32; ++w) {
+    uint32_t v = st.next32();
+    for (int b = 0; b < 32; ++b) r[w * 32 + b] = (uint8_t)((v >> b) & 1u);
+  }
+  int32_t u[N0];
+  for (int i = 0; i < N0; ++i) u[i] = (int32_t)g.sample(st);
+  for (int t = 0; t < N0; ++t) {
+    if (!r[t]) continue;
+    for (int i = 0; i < N0 - t; ++i) u[i + t] += A[i];
+    for (int i = N0 - t; i < N0; ++i) u[i + t - N0] -= A[i];
+  }
+  for (int i = 0; i < N0; ++i) ca[i] = (uint16_t)(((u[i] % Q0) + Q0) % Q0);
+  for (int i = 0; i < CLUES; ++i) {
+    int32_t v = (int32_t)g.sample(st);
+    for (int t = 0; t <= i; ++t)
+      if (r[t]) v += B[i - t];
+    for (int t = i + 1; t < N0; ++t)
+      if (r[t]) v -= B[N0 + i - t];
+    cb[i] = (uint16_t)(((v % Q0) + Q0) % Q0);
+  }
+}
+
+// (c * s0)[i] of the negacyclic product, i < 7, words of c reduced mod 2048: <a^(i), s0> of the extraction.
+inline int32_t clue_dot(const uint16_t *c, const uint8_t *s0, int i) {
+  int32_t acc = 0;
+  for (int k = 0; k <= i; ++k) acc += (c[k] & (Q0 - 1)) * s0[i - k];
+  for (int k = i + 1; k < N0; ++k) acc -= (c[k] & (Q0 - 1)) * s0[N0 + i - k];
+  return acc;
+}
+
+uint64_t clue_noise_support() {
+  static const uint64_t k = (uint64_t)(Gaussian(SIGMA_CLUE).table().size() - 1);
+  return k;
+}
+}  // namespace
+}  // namespace omr
+
 extern "C" omr_status omr_gen_clues(const omr_secret_key_pack *sk, uint64_t seed, uint64_t first,
                                     size_t count, uint16_t *clue_a, uint16_t *clue_b,
                                     int nthreads) {
@@ -285,30 +332,135 @@ extern "C" omr_status omr_gen_clues(const omr_secret_key_pack *sk, uint64_t seed
     return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_gen_clues: NULL argument");
   const Gaussian g(SIGMA_CLUE);
   parallel_for(count, nthreads, [&](size_t m) {
-    Stream st(seed, DOM_CLUE, first + m);
-    uint8_t r[N0];
-    for (int w = 0; w < N0 / 32; ++w) {
-      uint32_t v = st.next32();
-      for (int b = 0; b < 32; ++b) r[w * 32 + b] = (uint8_t)((v >> b) & 1u);
-    }
-    int32_t u[N0];
-    for (int i = 0; i < N0; ++i) u[i] = (int32_t)g.sample(st);
-    for (int t = 0; t < N0; ++t) {
-      if (!r[t]) continue;
-      const uint16_t *A = sk->pk_a;
-      for (int i = 0; i < N0 - t; ++i) u[i + t] += A[i];
-      for (int i = N0 - t; i < N0; ++i) u[i + t - N0] -= A[i];
-    }
-    uint16_t *ca = clue_a + m * N0;
-    for (int i = 0; i < N0; ++i) ca[i] = (uint16_t)(((u[i] % Q0) + Q0) % Q0);
+    clue_body(sk->pk_a, sk->pk_b, g, seed, first + m, clue_a + m * N0, clue_b + m * CLUES);
+  });
+  return OMR_OK;
+}
+
+// ==========================================================================================
+// Sender (include/omr_gpu.h "Sender"): the clue key as a value, its checks, the sender handle and the
+// recipient's clue opening on the CPU. The device entries are in keygen_gpu.hip.
+// ==========================================================================================
+extern "C" omr_status omr_secret_clue_key(const omr_secret_key_pack *sk, omr_clue_key *out) {
+  if (!sk || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_secret_clue_key: NULL argument");
+  memcpy(out->a, sk->pk_a, sizeof(out->a));
+  memcpy(out->b, sk->pk_b, sizeof(out->b));
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_clue_key_validate(const omr_clue_key *keys, size_t n_keys, uint64_t *noncanonical) {
+  if (!noncanonical || (n_keys && !keys))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_key_validate: NULL argument");
+  uint64_t n = 0;
+  for (size_t k = 0; k < n_keys; ++k)
+    for (int i = 0; i < N0; ++i) n += (keys[k].a[i] >= Q0) + (keys[k].b[i] >= Q0);
+  *noncanonical = n;
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_clue_key_noise_support(uint64_t *K) {
+  if (!K) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_key_noise_support: K is NULL");
+  *K = clue_noise_support();
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_clue_key_audit(const omr_secret_key_pack *sk, const omr_clue_key *key, uint64_t limit,
+                                         uint64_t *max_abs_noise, uint32_t *coeffs_over, uint32_t *noncanonical) {
+  if (!sk || !key) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_key_audit: NULL argument");
+  if (limit == UINT64_MAX) limit = clue_noise_support();
+  int32_t as[N0] = {0};  // A * s0, negacyclic, words reduced mod 2048
+  uint32_t nc = 0, over = 0;
+  uint64_t mx = 0;
+  for (int i = 0; i < N0; ++i) nc += (key->a[i] >= Q0) + (key->b[i] >= Q0);
+  for (int t = 0; t < N0; ++t) {
+    if (!sk->s0[t]) continue;
+    for (int i = 0; i < N0 - t; ++i) as[i + t] += key->a[i] & (Q0 - 1);
+    for (int i = N0 - t; i < N0; ++i) as[i + t - N0] -= key->a[i] & (Q0 - 1);
+  }
+  for (int i = 0; i < N0; ++i) {
+    const int32_t e = ((((key->b[i] & (Q0 - 1)) - as[i]) % Q0 + Q0 + Q0 / 2) % Q0) - Q0 / 2;  // [-1024, 1023]
+    const uint64_t ab = (uint64_t)(e < 0 ? -e : e);
+    mx = std::max(mx, ab);
+    over += ab > limit;
+  }
+  if (max_abs_noise) *max_abs_noise = mx;
+  if (coeffs_over) *coeffs_over = over;
+  if (noncanonical) *noncanonical = nc;
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_sender_create(const omr_clue_key *keys, size_t n_keys, int device, omr_sender **out) {
+  if (!keys || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_create: NULL argument");
+  if (n_keys == 0 || n_keys > UINT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_create: n_keys must be in [1, 2^32)");
+  for (size_t k = 0; k < n_keys; ++k)
+    for (int i = 0; i < N0; ++i)
+      if (keys[k].a[i] >= Q0 || keys[k].b[i] >= Q0)
+        return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_create: key " + std::to_string(k) + " has a word >= 2048");
+  static_assert(sizeof(omr_clue_key) == 2 * N0 * sizeof(uint16_t), "omr_clue_key is a then b, no padding");
+  auto s = std::make_unique<omr_sender>();
+  s->n_keys = n_keys;
+  const uint16_t *words = reinterpret_cast<const uint16_t *>(keys);
+  s->keys.assign(words, words + n_keys * 2 * N0);
+  if (device >= 0) {
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device >= ndev) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_create: no such device");
+    HIP_TRY(hipSetDevice(device));
+    const Gaussian g(SIGMA_CLUE);
+    const unsigned long long none = SENDER_NO_ERROR;
+    HIP_TRY(s->d_keys.upload_sync(s->keys));
+    HIP_TRY(s->d_cdt.upload_sync(g.table()));
+    HIP_TRY(s->d_err.upload_sync(&none, 1));
+    s->cdt_n = (int)g.table().size();
+    s->device = device;
+  }
+  *out = s.release();
+  return OMR_OK;
+}
+
+extern "C" void omr_sender_destroy(omr_sender *s) {
+  if (!s) return;
+  if (s->device >= 0) (void)hipSetDevice(s->device);
+  delete s;
+}
+
+extern "C" omr_status omr_sender_gen_clues(const omr_sender *s, const uint32_t *recipient, uint64_t seed, uint64_t first,
+                                           size_t count, uint16_t *clue_a, uint16_t *clue_b, int nthreads) {
+  if (!s || (count && (!clue_a || !clue_b)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_gen_clues: NULL argument");
+  if (recipient)
+    for (size_t m = 0; m < count; ++m)
+      if (recipient[m] >= s->n_keys)
+        return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_gen_clues: recipient of message " + std::to_string(m) +
+                                                       " is not a key of the table");
+  const Gaussian g(SIGMA_CLUE);
+  parallel_for(count, nthreads, [&](size_t m) {
+    const uint16_t *key = s->keys.data() + (size_t)(recipient ? recipient[m] : 0) * 2 * N0;
+    clue_body(key, key + N0, g, seed, first + m, clue_a + m * N0, clue_b + m * CLUES);
+  });
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_clue_open(const omr_secret_key_pack *sk, const uint16_t *clue_a, const uint16_t *clue_b,
+                                    size_t count, uint8_t *values, uint8_t *pertinent, uint8_t *max_abs_noise,
+                                    int nthreads) {
+  if (!sk || (!values && !pertinent && !max_abs_noise))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_open: NULL secret key pack or no output requested");
+  if (count == 0) return OMR_OK;
+  if (!clue_a || !clue_b) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_open: NULL clues");
+  parallel_for(count, nthreads, [&](size_t m) {
+    int any = 0, mx = 0;
     for (int i = 0; i < CLUES; ++i) {
-      int32_t v = (int32_t)g.sample(st);
-      for (int t = 0; t <= i; ++t)
-        if (r[t]) v += sk->pk_b[i - t];
-      for (int t = i + 1; t < N0; ++t)
-        if (r[t]) v -= sk->pk_b[N0 + i - t];
-      clue_b[m * CLUES + i] = (uint16_t)(((v % Q0) + Q0) % Q0);
+      const int phase = (((clue_b[m * CLUES + i] & (Q0 - 1)) - clue_dot(clue_a + m * N0, sk->s0, i)) % Q0 + Q0) % Q0;
+      const int value = ((8 * phase + Q0 / 2) >> 11) & 7;
+      const int noise = ((phase - 256 * value + Q0 + Q0 / 2) % Q0) - Q0 / 2;  // [-128, 127]
+      any |= value;
+      mx = std::max(mx, noise < 0 ? -noise : noise);
+      if (values) values[m * CLUES + i] = (uint8_t)value;
     }
+    if (pertinent) pertinent[m] = (uint8_t)(any == 0);
+    if (max_abs_noise) max_abs_noise[m] = (uint8_t)mx;
   });
   return OMR_OK;
 }

@@ -3,6 +3,8 @@
 // bit-identical to theirs whichever device, shard or thread count produces it:
 //   omr_gen_clues_device             Sender::gen_clues (sender.rs:27-32, key_gen/clue.rs:27-34)
 //   omr_keygen_detection_key_device  SecretKeyPack::generate_detector (key_gen/secret.rs:118-178)
+//   omr_sender_gen_clues_device      the same clues under a table of public clue keys (sender_kernels.hpp)
+//   omr_clue_open_device             SecretKeyPack::decrypt_clue (secret.rs:267-270) for a whole board
 // and the seeded detection key (include/omr_gpu.h): its generator, the mask rows and the expansion.
 //
 // Stream consumption is data dependent (rejection-sampled uniforms, Gaussians that draw a sign
@@ -22,6 +24,7 @@
 #include "host_ring.hpp"
 #include "kernels.hpp"
 #include "rng.hpp"
+#include "sender.hpp"
 
 using namespace omr;
 
@@ -172,6 +175,8 @@ __global__ __launch_bounds__(64) void gen_clues_kernel(const uint16_t *__restric
   for (int j = 0; j < N0 / 64; ++j) clue_a[m * N0 + tid + 64 * j] = (uint16_t)(acc[j] & (Q0 - 1));
   if (tid < CLUES) clue_b[m * CLUES + tid] = (uint16_t)(accb & (Q0 - 1));
 }
+
+#include "sender_kernels.hpp"  // sender_clues_kernel, clue_open_kernel
 
 // ------------------------------------------------------------------------------------------
 // RLWE key rows (keygen.hip ggsw_row): a uniform, b = a*s + e (- sigma_scale * sigma_g(s)),
@@ -426,6 +431,66 @@ extern "C" omr_status omr_gen_clues_device(const omr_secret_key_pack *sk, uint64
     const size_t n = std::min(CHUNK, count - off);
     gen_clues_kernel<<<(unsigned)n, 64, 0, st>>>(dpk, dcdt, (int)g.table().size(), seed, first + off, n,
                                                 d_clue_a + off * N0, d_clue_b + off * CLUES);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  return OMR_OK;
+}
+
+// The sender's mixed-recipient board in one launch per 2^20 messages: the key table, the Gaussian table
+// and the error word are the handle's, uploaded once by omr_sender_create (keygen.hip).
+extern "C" omr_status omr_sender_gen_clues_device(omr_sender *s, const uint32_t *d_recipient, uint64_t seed,
+                                                  uint64_t first, size_t count, uint16_t *d_clue_a,
+                                                  uint16_t *d_clue_b, void *stream) {
+  if (!s || (count && (!d_clue_a || !d_clue_b)))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_gen_clues_device: NULL argument");
+  if (s->device < 0)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_gen_clues_device: the sender was created without a device");
+  if (count == 0) return OMR_OK;
+  if (s->cdt_n > CDT_LDS) return set_error(OMR_ERR_DEVICE, "omr_sender_gen_clues_device: CDT table too large");
+  std::lock_guard<std::mutex> lk(s->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  constexpr size_t CHUNK = 1u << 20;
+  for (size_t off = 0; off < count; off += CHUNK) {
+    const size_t n = std::min(CHUNK, count - off);
+    sender_clues_kernel<<<(unsigned)n, 64, 0, st>>>(s->d_keys, (uint32_t)s->n_keys,
+                                                   d_recipient ? d_recipient + off : nullptr, s->d_cdt, s->cdt_n, seed,
+                                                   first + off, n, off, d_clue_a + off * N0, d_clue_b + off * CLUES,
+                                                   s->d_err);
+    HIP_TRY(hipGetLastError());
+  }
+  unsigned long long bad = SENDER_NO_ERROR;
+  HIP_TRY(hipMemcpyAsync(&bad, s->d_err, sizeof(bad), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (bad != SENDER_NO_ERROR) {  // rearm the error word: the sender stays usable
+    const unsigned long long none = SENDER_NO_ERROR;
+    HIP_TRY(hipMemcpyAsync(s->d_err, &none, sizeof(none), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_sender_gen_clues_device: recipient of message " +
+                                                   std::to_string(bad) + " is not a key of the table");
+  }
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_clue_open_device(const omr_secret_key_pack *sk, const uint16_t *d_clue_a,
+                                           const uint16_t *d_clue_b, size_t count, uint8_t *d_values,
+                                           uint8_t *d_pertinent, uint8_t *d_max_abs_noise, void *stream) {
+  if (!sk || (!d_values && !d_pertinent && !d_max_abs_noise))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_open_device: NULL secret key pack or no output requested");
+  if (count == 0) return OMR_OK;
+  if (!d_clue_a || !d_clue_b) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_open_device: NULL clues");
+  if ((uintptr_t)d_clue_a & 15)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_clue_open_device: d_clue_a not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  S0Bits s0{};
+  for (int i = 0; i < N0; ++i) s0.w[i >> 5] |= (uint32_t)(sk->s0[i] & 1u) << (i & 31);
+  constexpr size_t PER_WG = (size_t)OPEN_WAVES * OPEN_PER_WAVE, CHUNK = PER_WG << 20;  // 2^20 workgroups per launch
+  for (size_t off = 0; off < count; off += CHUNK) {
+    const size_t n = std::min(CHUNK, count - off);
+    clue_open_kernel<<<(unsigned)((n + PER_WG - 1) / PER_WG), 64 * OPEN_WAVES, 0, st>>>(
+        s0, d_clue_a + off * N0, d_clue_b + off * CLUES, n, d_values ? d_values + off * CLUES : nullptr,
+        d_pertinent ? d_pertinent + off : nullptr, d_max_abs_noise ? d_max_abs_noise + off : nullptr);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(st));

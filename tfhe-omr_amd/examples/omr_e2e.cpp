@@ -6,7 +6,7 @@
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
 //           [--compact BITS] [--audit-key] [--indexed-weights] [--seek-weights] [--device-retrieve]
-//           [--host-only]
+//           [--sender] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
 // PIECE messages instead of omr_detect_batch plus the encoders: no pertinency vector on the host.
@@ -42,6 +42,11 @@
 // (or a session from omr_digest_begin_seek), the recipient solves with omr_retrieve_payloads_seek, which builds its
 // own seek (with --device-retrieve: omr_auditor_retrieve_payloads_seek, on the auditor's device). With --host-only
 // it checks omr_payload_weights_at against omr_payload_weights' table on the pertinent set.
+// --sender plays the sender as a party of its own (include/omr_gpu.h, "Sender"): the board comes from one
+// omr_sender_gen_clues over the two packs' public clue keys (recipient 0, the detector's pack, where a message
+// is pertinent, 1 elsewhere) instead of two full generations and a merge; the recipient audits the clue key it
+// published (omr_clue_key_audit) and opens the board (omr_clue_open), whose pertinent set must be the board's,
+// before anything is detected. The rest of the flow is unchanged; with --host-only these CPU parts run.
 // --host-only runs the CPU parts of the ABI (keys, clues, weights, retrieval parameters) without
 // a GPU (used by the CPU test suite).
 #include <algorithm>
@@ -83,7 +88,7 @@ int main(int argc, char **argv) {
   uint64_t seed = 2025;
   bool host_only = false;
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
-  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false, seek_weights = false, device_retrieve = false;
+  bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false, seek_weights = false, device_retrieve = false, sender = false;
   int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -99,11 +104,12 @@ int main(int argc, char **argv) {
     else if (a == "--indexed-weights") indexed = true;
     else if (a == "--seek-weights") seek_weights = true;
     else if (a == "--device-retrieve") device_retrieve = true;
+    else if (a == "--sender") sender = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
                    "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--seek-weights] "
-                   "[--device-retrieve] [--host-only]\n",
+                   "[--device-retrieve] [--sender] [--host-only]\n",
                    argv[0]);
       return 2;
     }
@@ -164,15 +170,51 @@ int main(int argc, char **argv) {
 
   // Sender::gen_clues for every message (omr.rs:126-135)
   t = clk::now();
-  std::vector<uint16_t> ca(D * N0), cb(D * CLUES), xa(D * N0), xb(D * CLUES);
-  CHECK(omr_gen_clues(pa, seed + 1, 0, D, ca.data(), cb.data(), 0));
-  CHECK(omr_gen_clues(pb, seed + 2, 0, D, xa.data(), xb.data(), 0));
-  for (size_t m = 0; m < D; ++m)
-    if (!is_pert[m]) {
-      std::copy_n(&xa[m * N0], N0, &ca[m * N0]);
-      std::copy_n(&xb[m * CLUES], CLUES, &cb[m * CLUES]);
+  std::vector<uint16_t> ca(D * N0), cb(D * CLUES);
+  if (sender) {
+    // the sender holds the two public clue keys and nothing else: one generation, each message under its recipient
+    omr_clue_key keys[2];
+    CHECK(omr_secret_clue_key(pa, &keys[0]));
+    CHECK(omr_secret_clue_key(pb, &keys[1]));
+    std::vector<uint32_t> recipient(D);
+    for (size_t m = 0; m < D; ++m) recipient[m] = is_pert[m] ? 0 : 1;
+    omr_sender *snd = nullptr;
+    CHECK(omr_sender_create(keys, 2, -1, &snd));
+    CHECK(omr_sender_gen_clues(snd, recipient.data(), seed + 1, 0, D, ca.data(), cb.data(), 0));
+    omr_sender_destroy(snd);
+    std::printf("gen clues time: %.3f s (one sender over 2 clue keys)\n", secs(t));
+    // the recipient's checks: the key it published, and which messages of the board are its own
+    uint64_t K = 0, key_max = 0;
+    uint32_t over = 0, noncanon = 0;
+    CHECK(omr_clue_key_noise_support(&K));
+    CHECK(omr_clue_key_audit(pa, &keys[0], UINT64_MAX, &key_max, &over, &noncanon));
+    std::vector<uint8_t> opened(D), open_noise(D);
+    CHECK(omr_clue_open(pa, ca.data(), cb.data(), D, nullptr, opened.data(), open_noise.data(), 0));
+    size_t wrong = 0, n_open = 0;
+    uint8_t worst = 0;
+    for (size_t m = 0; m < D; ++m) {
+      wrong += (opened[m] != 0) != (is_pert[m] != 0);
+      n_open += opened[m] != 0;
+      if (opened[m]) worst = std::max(worst, open_noise[m]);
     }
-  std::printf("gen clues time: %.3f s\n", secs(t));
+    std::printf("sender: clue key max |e| %llu (support %llu), %u over, %u non-canonical words; %zu of %zu clues open as "
+                "pertinent, max |noise| %u of 128\n",
+                (unsigned long long)key_max, (unsigned long long)K, over, noncanon, n_open, D, (unsigned)worst);
+    if (over || noncanon || wrong) {
+      std::printf("Fail: %s\nFAILED\n", wrong ? "omr_clue_open's pertinent set is not the board's" : "the clue key fails its audit");
+      return 1;
+    }
+  } else {
+    std::vector<uint16_t> xa(D * N0), xb(D * CLUES);
+    CHECK(omr_gen_clues(pa, seed + 1, 0, D, ca.data(), cb.data(), 0));
+    CHECK(omr_gen_clues(pb, seed + 2, 0, D, xa.data(), xb.data(), 0));
+    for (size_t m = 0; m < D; ++m)
+      if (!is_pert[m]) {
+        std::copy_n(&xa[m * N0], N0, &ca[m * N0]);
+        std::copy_n(&xb[m * CLUES], CLUES, &cb[m * CLUES]);
+      }
+    std::printf("gen clues time: %.3f s\n", secs(t));
+  }
 
   // Payload::random (omr.rs:140-146)
   std::vector<uint16_t> payloads(D * PAYLOAD);

@@ -109,6 +109,22 @@ EXPORTS = {
                                        C.c_void_p]),
     "omr_keygen_detection_key_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),
+    # sender (include/omr_gpu.h "Sender"); omr_clue_key pointers are void *
+    "omr_secret_clue_key": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "omr_clue_key_validate": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "omr_clue_key_noise_support": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "omr_clue_key_audit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "omr_sender_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    "omr_sender_destroy": (None, [C.c_void_p]),
+    "omr_sender_gen_clues": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_int]),
+    "omr_sender_gen_clues_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "omr_clue_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_int]),
+    "omr_clue_open_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "omr_keygen_seeded_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _u32p, _u32p, _u64p, _u64p, C.c_int]),
     "omr_keygen_seeded_key_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
@@ -576,6 +592,123 @@ class SecretKeyPack:
                                    d_trace_key_b: int, stream: int = 0):
         _check(lib().omr_keygen_seeded_key_device(self._h, seed, mask_seed, d_bsk1_b, d_ksk_b, d_bsk2_b,
                                                   d_trace_key_b, stream or None), "omr_keygen_seeded_key_device")
+
+    # Sender side and clue opening (include/omr_gpu.h "Sender")
+    def clue_key(self) -> "ClueKey":
+        """SecretKeyPack::generate_clue_key (key_gen/secret.rs:99-107): the public key a sender needs."""
+        w = np.empty((2, N0), np.uint16)
+        _check(lib().omr_secret_clue_key(self._h, w.ctypes.data), "omr_secret_clue_key")
+        return ClueKey(w[0], w[1])
+
+    def open_clues(self, clue_a, clue_b, values: bool = True, pertinent: bool = True, noise: bool = True,
+                   nthreads: int = 0) -> dict:
+        """SecretKeyPack::decrypt_clue (secret.rs:267-270) for all 7 clues of each message, on the CPU:
+        values u8 [count][7], pertinent u8 [count], max_abs_noise u8 [count] (those asked for)."""
+        a = np.ascontiguousarray(clue_a, np.uint16).reshape(-1, N0)
+        b = np.ascontiguousarray(clue_b, np.uint16).reshape(-1, CLUE_COUNT)
+        n = a.shape[0]
+        assert b.shape[0] == n
+        out = {}
+        if values:
+            out["values"] = np.empty((n, CLUE_COUNT), np.uint8)
+        if pertinent:
+            out["pertinent"] = np.empty(n, np.uint8)
+        if noise:
+            out["max_abs_noise"] = np.empty(n, np.uint8)
+        ptr = [out[k].ctypes.data if k in out else None for k in ("values", "pertinent", "max_abs_noise")]
+        _check(lib().omr_clue_open(self._h, a.ctypes.data, b.ctypes.data, n, ptr[0], ptr[1], ptr[2], nthreads),
+               "omr_clue_open")
+        return out
+
+    def open_clues_device(self, d_clue_a: int, d_clue_b: int, count: int, d_values: int = 0, d_pertinent: int = 0,
+                          d_max_abs_noise: int = 0, stream: int = 0) -> None:
+        """The same on device buffers of the current HIP device; returns when the stream is done."""
+        _check(lib().omr_clue_open_device(self._h, d_clue_a or None, d_clue_b or None, count, d_values or None,
+                                          d_pertinent or None, d_max_abs_noise or None, stream or None),
+               "omr_clue_open_device")
+
+
+@dataclass
+class ClueKey:
+    """omr_clue_key: LwePublicKeyRlweMode (A, B = A s0 + E) over Z_2048[X]/(X^512 + 1), u16 [512] each."""
+    a: np.ndarray
+    b: np.ndarray
+
+    def words(self) -> np.ndarray:
+        """The wire form, u16 [2][512]."""
+        return np.stack([np.asarray(self.a, np.uint16).reshape(N0), np.asarray(self.b, np.uint16).reshape(N0)])
+
+
+def _clue_key_table(keys) -> np.ndarray:
+    """ClueKey, a sequence of them, or an array [n][2][512] -> contiguous u16 [n][2][512]."""
+    if isinstance(keys, ClueKey):
+        keys = [keys]
+    if not isinstance(keys, np.ndarray):
+        keys = np.stack([k.words() for k in keys]) if len(keys) else np.empty((0, 2, N0), np.uint16)
+    return np.ascontiguousarray(keys, np.uint16).reshape(-1, 2, N0)
+
+
+def clue_key_noise_support() -> int:
+    k = C.c_uint64()
+    _check(lib().omr_clue_key_noise_support(C.byref(k)), "omr_clue_key_noise_support")
+    return k.value
+
+
+def validate_clue_keys(keys) -> int:
+    """The words >= 2048 of a table of clue keys (reports, does not reject)."""
+    t = _clue_key_table(keys)
+    n = C.c_uint64()
+    _check(lib().omr_clue_key_validate(t.ctypes.data, t.shape[0], C.byref(n)), "omr_clue_key_validate")
+    return n.value
+
+
+def audit_clue_key(secret: "SecretKeyPack", key, limit: int = None) -> dict:
+    """omr_clue_key_audit: the noise B - A s0 of a clue key against the pack's s0 (limit None = K)."""
+    t = _clue_key_table(key)
+    assert t.shape[0] == 1
+    mx, over, nc = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    _check(lib().omr_clue_key_audit(secret._h, t.ctypes.data, (1 << 64) - 1 if limit is None else limit,
+                                    C.byref(mx), C.byref(over), C.byref(nc)), "omr_clue_key_audit")
+    return dict(max_abs_noise=mx.value, coeffs_over=over.value, noncanonical=nc.value)
+
+
+class Sender:
+    """Sender::new / Sender::gen_clues (sender.rs:27-32) over a table of public clue keys: the clue of
+    global message index first + m under key recipient[m]. device None: CPU only."""
+
+    def __init__(self, keys, device: int = None):
+        t = _clue_key_table(keys)
+        h = C.c_void_p()
+        _check(lib().omr_sender_create(t.ctypes.data, t.shape[0], -1 if device is None else device, C.byref(h)),
+               "omr_sender_create")
+        self._h = h
+        self.n_keys = t.shape[0]
+        self._destroy = lib().omr_sender_destroy
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def gen_clues(self, seed: int, first: int, count: int, recipient=None, nthreads: int = 0, out=None):
+        """(clue_a u16 [count][512], clue_b u16 [count][7]); out = (clue_a, clue_b) writes into given arrays."""
+        a, b = out if out is not None else (np.empty((count, N0), np.uint16), np.empty((count, CLUE_COUNT), np.uint16))
+        assert a.dtype == np.uint16 and b.dtype == np.uint16 and a.size == count * N0 and b.size == count * CLUE_COUNT
+        assert a.flags.c_contiguous and b.flags.c_contiguous
+        r = None if recipient is None else np.ascontiguousarray(recipient, np.uint32)
+        assert r is None or r.shape == (count,)
+        _check(lib().omr_sender_gen_clues(self._h, None if r is None else r.ctypes.data, seed, first, count,
+                                          a.ctypes.data, b.ctypes.data, nthreads), "omr_sender_gen_clues")
+        return a, b
+
+    def gen_clues_device(self, seed: int, first: int, count: int, d_clue_a: int, d_clue_b: int, d_recipient: int = 0,
+                         stream: int = 0) -> None:
+        """The same bits into device buffers of the sender's device; d_recipient u32 [count] or 0."""
+        _check(lib().omr_sender_gen_clues_device(self._h, d_recipient or None, seed, first, count, d_clue_a or None,
+                                                 d_clue_b or None, stream or None), "omr_sender_gen_clues_device")
 
 
 # ---- on-disk container (SURVEY.md §8 f3; the reference has no serialization) ----------------
