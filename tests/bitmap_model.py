@@ -4,7 +4,8 @@ independent of the library:
   message g -> ciphertext c = g // 16384, l = g % 16384, coefficient j = l % 2048, bit t = l // 2048
   out[c][h][i] = sum_g pv_g[h][i] * 2^t * psi^((2 brv11(i) + 1) j mod 4096)  mod q2,  psi = 22^((q2 - 1) / 4096)
 
-and the kernel test's cases with their expected outputs, computed once per process."""
+and the kernel test's cases with their expected outputs, computed once per process. These are random
+words at six shapes; the crafted residues, sums and shapes are tests/bitmap_cases.py's, over this model."""
 import functools
 
 import numpy as np

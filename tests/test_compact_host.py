@@ -38,25 +38,7 @@ def test_cpu_equals_model_on_the_shared_cases(bits):
         assert got[i].tobytes() == M.compact_coefficients(ca, cb, bits), f"{names[i]} at {bits} bits"
 
 
-def step(y, bits):
-    """The smallest x that rounds to y (y >= 1): ceil((2 q2 y - q2) / (2 Q))."""
-    q = 1 << bits
-    return -((-(2 * Q2 * y - Q2)) // (2 * q))
-
-
-def crafted_coefficients(bits):
-    """Coefficient vectors with x = 0, q2 - 1 (wraps to 0) and the x on either side of a rounding step at
-    coefficients 0, 1, 255, 256 and 2047; two vectors, used as a and b."""
-    q = 1 << bits
-    pos = [0, 1, 255, 256, 2047]
-    ys = [1, q // 2, q - 1, q, 12345 % q + 1]
-    lo, hi = [7] * N2, [Q2 // 3] * N2
-    for p, y in zip(pos, ys):
-        lo[p], hi[p] = step(y, bits) - 1, step(y, bits)
-    edge = [0] * N2
-    for p, x in zip(pos, [0, Q2 - 1, Q2 - 1, 0, Q2 - 1]):
-        edge[p] = x
-    return [lo, hi, edge], pos, ys
+step, crafted_coefficients = M.step, M.crafted_coefficients
 
 
 @pytest.mark.parametrize("bits", [16, 19, 27, 32])
@@ -80,6 +62,51 @@ def test_crafted_rounding_steps(bits):
     assert [vals[p] for p in pos] == [y % q for y in ys]
     vals = M.unpack(got[2].tobytes()[:256 * bits], bits)
     assert not any(vals)
+
+
+@pytest.mark.parametrize("bits", [16, 19, 27, 32])
+def test_step_ladder_and_the_five_crafted_ciphertexts(bits):
+    """What the device test sends: every coefficient on a step of its own, y from 1 to Q, either side."""
+    q = 1 << bits
+    lo, hi, ys = M.step_ladder(bits)
+    assert ys[0] == 1 and ys[-1] == q and all(a < b for a, b in zip(ys, ys[1:]))
+    assert all(M.rescale(x, bits) == y - 1 for x, y in zip(lo, ys))
+    assert all(M.rescale(x, bits) == y % q for x, y in zip(hi, ys)) and max(hi) < Q2
+    assert 2 * hi[-1] << bits >= 2**64  # 2 x Q does not fit 64 bits
+    cts, pairs = M.crafted_cts(bits)
+    got = A.compact_cts_cpu(cts, bits)
+    for i, (ca, cb) in enumerate(pairs):
+        assert got[i].tobytes() == M.compact_coefficients(ca, cb, bits), (i, bits)
+    (_, _, _), pos, cys = M.crafted_coefficients(bits)
+    assert pos == [0, 1, 255, 256, 257, 2047] and {q - 1, q} <= set(cys)
+
+
+@pytest.mark.parametrize("bits", ALL_BITS)
+def test_expand_streams_are_what_they_claim(bits):
+    """The packed streams of the device's expand test: 0, 1, Q / 2 and Q - 1 at the first and the last value and
+    at values that end on, start on and straddle a 32-bit word, each of the four at every such position."""
+    q = 1 << bits
+    starts, ends, straddles = M.stream_positions(bits)
+    assert starts[0] == 0 and ends[-1] == N2 - 1
+    assert bool(straddles) == (bits not in (16, 32))  # at 16 and 32 bits no value lies across a word
+    for i in straddles[:8]:
+        assert (i * bits) % 32 + bits > 32
+    pos = M.expand_positions(bits)
+    assert {0, N2 - 1, starts[1], ends[0], ends[-2]} <= set(pos) and (not straddles or {straddles[0], straddles[-1]} <= set(pos))
+    vals = M.expand_values(bits)
+    for i in pos:
+        assert {v[i] for v in vals} == {0, 1, q // 2, q - 1}
+    packed = M.expand_streams(bits)
+    assert packed.shape == (2, 512 * bits)
+    for k in range(4):
+        half = packed[k // 2].tobytes()[(k % 2) * 256 * bits:(k % 2 + 1) * 256 * bits]
+        assert M.unpack(half, bits) == vals[k]
+    back = A.compact_expand_cpu(packed, bits)
+    assert int(back.max()) < Q2
+    if bits in (16, 19, 27, 32):  # the model's transform is Python's: four widths
+        for i in range(2):
+            assert np.array_equal(back[i], M.expand(packed[i].tobytes(), bits))
+    assert M.unscale(q - 1, bits) < Q2 and M.unscale(0, bits) == 0 and M.unscale(q // 2, bits) == (Q2 + 1) // 2
 
 
 @pytest.mark.parametrize("bits", [16, 20, 24, 31, 32])

@@ -1,7 +1,10 @@
 """Compact ciphertexts on the GPU (include/omr_gpu.h, "Compact ciphertexts"): compact_kernel through
 omr_compact_cts_device / omr_compact_cts and expand_kernel through omr_compact_expand_device /
 omr_audit_compact against the CPU statement (which test_compact_host.py pins to the Python-integer model),
-byte for byte, for every width and launch shape; then one real board through a digest session:
+byte for byte, for every width and launch shape; the crafted inputs of compact_model.py against the CPU statement
+and the model: coefficients on either side of a rounding step, where the device's FP64 quotient estimate and its
+correction decide, and packed streams with boundary values at every kind of stream-word position; then one real
+board through a digest session:
 omr_digest_read_compact, retrieval from the expanded digest, the residual increase against R(bits), and the
 session call's argument rules. Every comparison is exact equality."""
 import ctypes as C
@@ -10,6 +13,7 @@ import numpy as np
 import pytest
 
 import audit_cases as AC
+import compact_model as M
 import product_lib as PL
 import test_gpu_digest_session as DS
 from product_lib import omr_amd as A
@@ -136,6 +140,46 @@ def test_more_ciphertexts_than_the_grid(g, bits):
     assert np.array_equal(got, A.compact_expand_cpu(want, bits))
     assert np.array_equal(compact_device(g, g.d_many, MANY, bits), want)
     assert np.array_equal(g.det.compact_cts(g.many[:70], bits), want[:70])
+
+
+@pytest.mark.parametrize("bits", ALL_BITS)
+def test_rounding_steps_on_the_device(g, bits):
+    """compact_rescale as the device compiles it, on either side of a step: the three crafted ciphertexts (steps
+    y = 1, Q / 2, Q - 1 and Q at the thread and register edges, q2 - 1 wrapping to 0) and the ladder (all 2,048
+    coefficients one below, and at, a step of their own, y from 1 to Q), through the device and the host entry,
+    by one workgroup and by the default grid, against the CPU statement and the Python-integer model."""
+    cts, pairs = M.crafted_cts(bits)
+    want = A.compact_cts_cpu(cts, bits)
+    for i, (ca, cb) in enumerate(pairs):
+        assert want[i].tobytes() == M.compact_coefficients(ca, cb, bits), i
+    d_cts = dev(cts)
+    for grid in (1, 0):
+        g.det.set_compact_grid(grid)
+        try:
+            got_device = compact_device(g, d_cts, len(pairs), bits)
+            got_host = g.det.compact_cts(cts, bits)
+        finally:
+            g.det.set_compact_grid(0)
+        assert np.array_equal(got_device, want), (grid, np.argwhere(got_device != want)[:5])
+        assert np.array_equal(got_host, want), grid
+
+
+@pytest.mark.parametrize("bits", ALL_BITS)
+def test_expand_boundary_values_on_the_device(g, bits):
+    """expand_kernel on streams with y = 0, 1, Q / 2 and Q - 1 at the first and the last value and at values that
+    end on, start on and straddle a 32-bit stream word, against omr_compact_expand_cpu and the model."""
+    packed = M.expand_streams(bits)
+    want = A.compact_expand_cpu(packed, bits)
+    for i in range(packed.shape[0]):
+        assert np.array_equal(want[i], M.expand(packed[i].tobytes(), bits)), i
+    assert int(want.max()) < Q2
+    for grid in (1, 0):
+        g.aud.set_grid(grid)
+        try:
+            got = expand_device(g, packed, bits)
+        finally:
+            g.aud.set_grid(0)
+        assert np.array_equal(got, want), (grid, np.argwhere(got != want)[:5])
 
 
 @pytest.mark.parametrize("bits,staging", [(24, 0), (20, 2), (16, 1), (32, 0)])
