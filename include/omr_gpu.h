@@ -836,6 +836,81 @@ omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *sk, const ui
                                          uint16_t *payloads);
 
 /* ---------------------------------------------------------------------------------------
+ * Payload length as a board parameter (none in the reference): indexed payload digests whose payloads are
+ * L words long, 1 <= L <= OMR_PAYLOAD_LEN_MAX, instead of the 612 of OMR_PAYLOAD_LEN. The reference's own
+ * recipient can only read 612-word payloads, so the table and seek conventions stay at 612; the length
+ * belongs to the indexed convention, the one for parties not bound to the reference.
+ *
+ * Layout of a board with payload length L and pertinent_count pertinent messages:
+ *   stripes           = ceil(L / 2048), at most 8
+ *   per               = min(2048 / L, OMR_PAYLOAD_PER_CT_MAX) combinations per ciphertext for L <= 2048,
+ *                       1 for L > 2048
+ *   combination_count = pertinent_count + 5, as in omr_get_retrieval_params
+ *   groups            = ceil(combination_count / per),  payload_ct = groups * stripes
+ * Ciphertext c is stripe s = c % stripes of group c / stripes, which holds the combinations
+ * (c / stripes) * per + j for j < per. A combination at or beyond combination_count is padding, with
+ * weight 0. With one stripe, slot j * L + l holds centred_lift(payload[l] * w(combo, g) mod 257) for l < L
+ * and every other slot is 0. With several stripes (per = 1), slot i of stripe s holds that value for word
+ * l = 2048 * s + i when l < L, and 0 otherwise. w is omr_indexed_weights_at's weight, unchanged, and so are
+ * the centred lift, the NTT and the sum mod q2. L = 612 at 3 combinations per ciphertext fills a ciphertext
+ * that omr_get_retrieval_params fills with 2. The cap of 16 combinations keeps the weights a workgroup
+ * stages at 16 x 144 u16 of LDS: below L = 128 a ciphertext is not full (16 L < 2048 slots are used).
+ * ------------------------------------------------------------------------------------- */
+#define OMR_PAYLOAD_LEN_MAX 16384
+#define OMR_PAYLOAD_PER_CT_MAX 16
+typedef struct {
+  uint32_t payload_len, combination_count, cmb_count_per_cipher, stripes, payload_ct;
+} omr_payload_layout;
+/* The layout above. OMR_ERR_INVALID_ARGUMENT for NULL, payload_len = 0 or above OMR_PAYLOAD_LEN_MAX, or a
+ * pertinent_count whose combination count does not fit 32 bits. */
+omr_status omr_get_payload_layout(size_t pertinent_count, size_t payload_len, omr_payload_layout *out);
+/* omr_encode_payloads_indexed_device for payloads u16 [D][payload_len]. first_ct and n_ct count ciphertexts,
+ * stripes included: the call covers the ciphertexts [first_ct, first_ct + n_ct) of the layout with cmb_per_ct
+ * combinations per group, so it may start or end in the middle of a stripe group. cmb_per_ct is explicit, as
+ * in omr_encode_payloads_indexed_device: any value in [1, per] (a digest is decoded with the value it was
+ * encoded with). A ciphertext that holds only padding is all zeros. payload_len = 612 with cmb_per_ct <= 3
+ * gives the bits of omr_encode_payloads_indexed_device. OMR_ERR_INVALID_ARGUMENT, before anything is
+ * enqueued, for NULL (seed included), n_ct = 0 or above 65,535, payload_len = 0 or above
+ * OMR_PAYLOAD_LEN_MAX, cmb_per_ct = 0 or above the layout's per for that length, D above INT32_MAX, or
+ * global_offset + D > all_payloads_count. */
+omr_status omr_encode_payloads_indexed_len_device(omr_ctx *ctx, const uint64_t *d_pv,
+                                                  const uint16_t *d_payloads /* [D][payload_len] */, size_t D,
+                                                  size_t global_offset, size_t all_payloads_count,
+                                                  const uint8_t seed[32], uint32_t combination_count,
+                                                  uint32_t payload_len, uint32_t cmb_per_ct, uint32_t first_ct,
+                                                  uint32_t n_ct, uint64_t *d_out /* [n_ct][2][2048] */,
+                                                  void *hip_stream);
+/* The same on host buffers; returns when done. */
+omr_status omr_encode_payloads_indexed_len(omr_ctx *ctx, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                           size_t global_offset, size_t all_payloads_count, const uint8_t seed[32],
+                                           uint32_t combination_count, uint32_t payload_len, uint32_t cmb_per_ct,
+                                           uint32_t first_ct, uint32_t n_ct, uint64_t *out);
+/* omr_digest_begin_indexed for a board whose payloads are payload_len words long: the session's updates take
+ * payloads u16 [D][payload_len], its payload digest has omr_get_payload_layout(pertinent_count, payload_len)'s
+ * payload_ct ciphertexts, and omr_digest_get_info reports that payload_ct and cmb_count_per_cipher. Merge,
+ * read, compact read, bitmap and omr_digest_device_bytes work unchanged on it; the index digest and the
+ * bitmap do not depend on the length. OMR_ERR_INVALID_ARGUMENT for a length out of range, or a layout of more
+ * than 65,535 payload ciphertexts (a session encodes them in one launch; such a board is encoded in groups
+ * with omr_encode_payloads_indexed_len_device). */
+omr_status omr_digest_begin_indexed_len(omr_ctx *ctx, size_t all_payloads_count, size_t pertinent_count,
+                                        uint64_t index_seed, const uint8_t weight_seed[32], size_t payload_len,
+                                        void *hip_stream, omr_digest **out);
+/* The payload layout of any session: of a 612-word session, payload_len 612, one stripe and
+ * omr_get_retrieval_params' counts. */
+omr_status omr_digest_get_payload_layout(omr_digest *dg, omr_payload_layout *layout);
+/* omr_retrieve_payloads_indexed for a digest of the layout given: payloads u16 [n_indices][payload_len]. The
+ * system has layout->combination_count rows; combination j's payload_len words are gathered across its
+ * stripes, and the solve is the same one with width = payload_len. Of the layout, payload_len,
+ * combination_count and cmb_count_per_cipher are read (stripes and payload_ct follow from them; n_ct must be at
+ * least ceil(combination_count / cmb_count_per_cipher) * stripes). The status codes of
+ * omr_retrieve_payloads_indexed, OMR_ERR_NOT_INVERTIBLE included; OMR_ERR_INVALID_ARGUMENT also for a NULL
+ * layout, a length out of range or a cmb_count_per_cipher the length does not allow. */
+omr_status omr_retrieve_payloads_indexed_len(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,
+                                             size_t all_payloads_count, const omr_payload_layout *layout,
+                                             const uint8_t weight_seed[32], const size_t *indices,
+                                             size_t n_indices, uint16_t *payloads);
+
+/* ---------------------------------------------------------------------------------------
  * Solve mod 257 — solve_matrix_mod_257 (matrix.rs:164-247), the elimination behind
  * Retriever::decode_digest, as an operation of its own: on the CPU, and on an auditor's device.
  *
@@ -897,6 +972,13 @@ omr_status omr_auditor_retrieve_payloads_indexed(omr_auditor *aud, const void *p
                                                  size_t all_payloads_count, uint32_t combination_count,
                                                  const uint8_t weight_seed[32], const size_t *indices,
                                                  size_t n_indices, uint16_t *payloads);
+/* omr_retrieve_payloads_indexed_len's device twin ("Payload length as a board parameter" above), for full and
+ * compact ciphertexts: the right-hand side is gathered across the stripes on the device and the solver runs
+ * with width = layout->payload_len. The same bits and status codes as the CPU entry. */
+omr_status omr_auditor_retrieve_payloads_indexed_len(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,
+                                                     size_t all_payloads_count, const omr_payload_layout *layout,
+                                                     const uint8_t weight_seed[32], const size_t *indices,
+                                                     size_t n_indices, uint16_t *payloads);
 /* decode_digest in one call, indexed weights: indices, then payloads of the indices found. The system
  * has the board's rp.combination_count rows. cap < found is OMR_ERR_INVALID_ARGUMENT with *found set.
  * summary (may be NULL) is added into with the audit of every ciphertext the call decoded (all of

@@ -51,6 +51,8 @@ pub mod ffi {
     pub const OMR_TRACE_DIGITS: usize = 25;
     pub const OMR_P: u32 = 257;
     pub const OMR_PAYLOAD_LEN: usize = 612;
+    pub const OMR_PAYLOAD_LEN_MAX: usize = 16384;
+    pub const OMR_PAYLOAD_PER_CT_MAX: u32 = 16;
 
     #[repr(C)]
     pub struct OmrSecretKeyPack {
@@ -156,6 +158,16 @@ pub mod ffi {
         pub combination_count: u32,
         pub cmb_count_per_cipher: u32,
         pub cmb_cipher_count: u32,
+    }
+    /// `omr_payload_layout`: the payload digest of a board whose payloads are `payload_len` words long.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+    pub struct OmrPayloadLayout {
+        pub payload_len: u32,
+        pub combination_count: u32,
+        pub cmb_count_per_cipher: u32,
+        pub stripes: u32,
+        pub payload_ct: u32,
     }
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
@@ -376,6 +388,32 @@ pub mod ffi {
                                              all_payloads_count: usize, combination_count: u32,
                                              weight_seed: *const u8, indices: *const usize, n_indices: usize,
                                              payloads: *mut u16) -> OmrStatus;
+
+        // payload length as a board parameter (none in the reference)
+        pub fn omr_get_payload_layout(pertinent_count: usize, payload_len: usize,
+                                      out: *mut OmrPayloadLayout) -> OmrStatus;
+        pub fn omr_encode_payloads_indexed_len_device(ctx: *mut OmrCtx, d_pv: *const u64, d_payloads: *const u16,
+                                                      d: usize, global_offset: usize, all_payloads_count: usize,
+                                                      seed: *const u8, combination_count: u32, payload_len: u32,
+                                                      cmb_per_ct: u32, first_ct: u32, n_ct: u32, d_out: *mut u64,
+                                                      hip_stream: *mut c_void) -> OmrStatus;
+        pub fn omr_encode_payloads_indexed_len(ctx: *mut OmrCtx, pv: *const u64, payloads: *const u16, d: usize,
+                                               global_offset: usize, all_payloads_count: usize, seed: *const u8,
+                                               combination_count: u32, payload_len: u32, cmb_per_ct: u32,
+                                               first_ct: u32, n_ct: u32, out: *mut u64) -> OmrStatus;
+        pub fn omr_digest_begin_indexed_len(ctx: *mut OmrCtx, all_payloads_count: usize, pertinent_count: usize,
+                                            index_seed: u64, weight_seed: *const u8, payload_len: usize,
+                                            hip_stream: *mut c_void, out: *mut *mut OmrDigest) -> OmrStatus;
+        pub fn omr_digest_get_payload_layout(dg: *mut OmrDigest, layout: *mut OmrPayloadLayout) -> OmrStatus;
+        pub fn omr_retrieve_payloads_indexed_len(sk: *const OmrSecretKeyPack, pay_cts: *const u64, n_ct: u32,
+                                                 all_payloads_count: usize, layout: *const OmrPayloadLayout,
+                                                 weight_seed: *const u8, indices: *const usize, n_indices: usize,
+                                                 payloads: *mut u16) -> OmrStatus;
+        pub fn omr_auditor_retrieve_payloads_indexed_len(aud: *mut OmrAuditor, pay_cts: *const c_void, n_ct: u32,
+                                                         bits: c_int, all_payloads_count: usize,
+                                                         layout: *const OmrPayloadLayout, weight_seed: *const u8,
+                                                         indices: *const usize, n_indices: usize,
+                                                         payloads: *mut u16) -> OmrStatus;
 
         // bitmap digest (none in the reference)
         pub fn omr_bitmap_ct_count(all_payloads_count: usize, n_ct: *mut u32) -> OmrStatus;

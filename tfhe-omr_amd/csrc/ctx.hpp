@@ -218,14 +218,16 @@ omr_status encode_indices(omr_ctx *c, const uint64_t *d_pv, size_t D, size_t off
                           uint32_t first_ct, uint32_t n_ct, uint64_t *d_out, hipStream_t st, bool accumulate);
 // Where a payload encode takes its weights from, one kind per device entry point and digest session.
 struct PayloadWeights {
-  enum Kind { TABLE, INDEXED, SEEK } kind = TABLE;
+  enum Kind { TABLE, INDEXED, SEEK, INDEXED_LEN } kind = TABLE;
   const uint16_t *d_table = nullptr;  // TABLE: [n_ct * per_ct][all] on the device, row 0 = first_ct's first
-  WeightKey key{};                    // INDEXED (weights.hpp, indexed_weight_block), SEEK: the weight seed
+  WeightKey key{};                    // INDEXED[_LEN] (weights.hpp, indexed_weight_block), SEEK: the weight seed
   omr_weight_seek seek{};             // SEEK (weights.hpp, "Reference payload weights by seek"): of combos * all draws
-  uint32_t combos = 0;                // INDEXED, SEEK: combinations from this one on are padding, weight 0
+  uint32_t combos = 0;                // INDEXED[_LEN], SEEK: combinations from this one on are padding, weight 0
+  uint32_t len = PAYLOAD_LEN;         // words per payload: INDEXED_LEN's board parameter, 612 for every other kind
 };
-// The body of the three omr_encode_payloads*_device entries: the ciphertexts [first_ct, first_ct + n_ct) of
-// per_ct combinations each; the kind picks the kernel (encode_kernels.hpp).
+// The body of the omr_encode_payloads*_device entries: the ciphertexts [first_ct, first_ct + n_ct) of
+// per_ct combinations each (INDEXED_LEN: per group of payload_stripes(len) ciphertexts); payloads
+// [D][weights.len]; the kind picks the kernel (encode_kernels.hpp).
 omr_status encode_payloads(omr_ctx *c, const uint64_t *d_pv, const uint16_t *d_payloads, size_t D, size_t offset,
                            size_t all, const PayloadWeights &weights, uint32_t first_ct, uint32_t n_ct,
                            uint32_t per_ct, uint64_t *d_out, hipStream_t st, bool accumulate);

@@ -8,7 +8,9 @@
 // omr_digest_read_compact hands the digest out in compact form (compact.hpp) and leaves it as it is.
 // A session from omr_digest_begin_indexed holds no weight table: its payload encode computes the indexed
 // weights (weights.hpp) in the kernel; one from omr_digest_begin_seek holds the seek of its board and the
-// kernel finds the reference's weights through it; everything else is shared.
+// kernel finds the reference's weights through it; one from omr_digest_begin_indexed_len has the payload length
+// as a parameter of its board ("Payload length as a board parameter"): its updates take payloads [D][len] and
+// its payload digest has that layout's ciphertexts; everything else is shared.
 //
 // The session owns its buffers (weights, digest, pertinency chunk, host staging) and borrows the
 // context's detect / encode scratch under the context mutex (ctx.hpp), like any other call.
@@ -31,7 +33,9 @@ struct omr_digest {
   uint64_t index_seed;
   omr_retrieval_params rp;
   DevBuf<uint16_t> table;        // [payload_ct * cmb_count_per_cipher][all]; only a table session has them
-  PayloadWeights weights;        // TABLE, INDEXED, SEEK: omr_digest_begin, _begin_indexed, _begin_seek
+  PayloadWeights weights;        // TABLE, INDEXED, SEEK, INDEXED_LEN: omr_digest_begin, _begin_indexed, _begin_seek,
+                                 // _begin_indexed_len; weights.len is the words per payload of the updates
+  omr_payload_layout ly;         // the payload digest's layout: rp's counts at 612 words, or the length's own
   DevBuf<uint64_t> digest;       // [index_ct + payload_ct][2][N2], canonical
   DevBuf<uint64_t> pv;           // pertinency ciphertexts of one piece, grown lazily
   DevBuf<uint64_t> merge_stage;  // omr_digest_merge's and omr_digest_merge_bitmap's upload
@@ -60,14 +64,14 @@ omr_status poisoned_error(const char *who) {
 omr_status ensure_piece(omr_digest *dg, size_t B, bool host) {
   const bool grow_pv = !dg->pv.fits(B * 2 * N2);
   const bool grow_stage = host && !(dg->s_clue_a.fits(B * N0) && dg->s_clue_b.fits(B * CLUES) &&
-                                    dg->s_payloads.fits(B * PAYLOAD_LEN));
+                                    dg->s_payloads.fits(B * dg->weights.len));
   if (!grow_pv && !grow_stage) return OMR_OK;
   HIP_TRY(hipStreamSynchronize(dg->st));
   if (grow_pv) HIP_TRY(dg->pv.reserve(B * 2 * N2));
   if (grow_stage) {
     HIP_TRY(dg->s_clue_a.reserve(B * N0));
     HIP_TRY(dg->s_clue_b.reserve(B * CLUES));
-    HIP_TRY(dg->s_payloads.reserve(B * PAYLOAD_LEN));
+    HIP_TRY(dg->s_payloads.reserve(B * dg->weights.len));
   }
   return OMR_OK;
 }
@@ -80,7 +84,7 @@ omr_status run_piece(omr_digest *dg, const uint16_t *ca, const uint16_t *cb, con
   if (host) {
     HIP_TRY(hipMemcpyAsync(dg->s_clue_a, ca, n * N0 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dg->s_clue_b, cb, n * CLUES * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dg->s_payloads, pay, n * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dg->s_payloads, pay, n * dg->weights.len * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     ca = dg->s_clue_a, cb = dg->s_clue_b, pay = dg->s_payloads;
   }
   OMR_TRY(detect_device(c, ca, cb, n, dg->pv, st));
@@ -115,7 +119,7 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
   }
   for (size_t o = 0; o < D; o += B) {
     const size_t n = std::min(B, D - o);
-    if ((s = run_piece(dg, ca + o * N0, cb + o * CLUES, pay + o * PAYLOAD_LEN, n, offset + o, host)) != OMR_OK) {
+    if ((s = run_piece(dg, ca + o * N0, cb + o * CLUES, pay + o * dg->weights.len, n, offset + o, host)) != OMR_OK) {
       dg->poisoned = true;  // part of the range may already be in the digest
       return s;
     }
@@ -130,22 +134,33 @@ omr_status digest_update(omr_digest *dg, const uint16_t *ca, const uint16_t *cb,
   return s;
 }
 
-// omr_digest_begin, omr_digest_begin_indexed and omr_digest_begin_seek: only the table session draws and
-// uploads weights; the seek session scans the stream for its rejections on the device.
+// omr_digest_begin, omr_digest_begin_indexed, omr_digest_begin_seek and omr_digest_begin_indexed_len: only the
+// table session draws and uploads weights; the seek session scans the stream for its rejections on the device;
+// only the INDEXED_LEN session reads payload_len, the others' payloads are 612 words in rp's layout.
 omr_status digest_begin(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed, const uint8_t weight_seed[32],
-                        void *stream, omr_digest **out, PayloadWeights::Kind kind, const char *who) {
+                        void *stream, omr_digest **out, PayloadWeights::Kind kind, const char *who,
+                        size_t payload_len = PAYLOAD_LEN) {
   if (!c || !weight_seed || !out) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
   *out = nullptr;
   omr_retrieval_params rp;
   omr_status s;
   OMR_TRY(omr_get_retrieval_params(all, pertinent, &rp));
+  omr_payload_layout ly{PAYLOAD_LEN, rp.combination_count, rp.cmb_count_per_cipher, 1, rp.cmb_cipher_count};
+  if (kind == PayloadWeights::INDEXED_LEN) {
+    OMR_TRY(omr_get_payload_layout(pertinent, payload_len, &ly));
+    if (ly.payload_ct > 65535)  // one piece encodes them all in one launch, the grid's y extent
+      return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": more than 65,535 payload ciphertexts");
+    rp.cmb_count_per_cipher = ly.cmb_count_per_cipher, rp.cmb_cipher_count = ly.payload_ct;
+  }
   HIP_TRY(hipSetDevice(c->device));
   try {
     std::unique_ptr<omr_digest> dg(new omr_digest(c, (hipStream_t)stream, all, index_seed));
     dg->rp = rp;
+    dg->ly = ly;
     PayloadWeights &pw = dg->weights;
     pw.kind = kind;
     pw.combos = rp.combination_count;
+    pw.len = ly.payload_len;
     if (kind != PayloadWeights::TABLE) {
       pw.key = weight_key(weight_seed);
       if (kind == PayloadWeights::SEEK)
@@ -183,6 +198,13 @@ extern "C" omr_status omr_digest_begin_indexed(omr_ctx *c, size_t all, size_t pe
                                                const uint8_t weight_seed[32], void *stream, omr_digest **out) {
   return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, PayloadWeights::INDEXED,
                       "omr_digest_begin_indexed");
+}
+
+extern "C" omr_status omr_digest_begin_indexed_len(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
+                                                   const uint8_t weight_seed[32], size_t payload_len, void *stream,
+                                                   omr_digest **out) {
+  return digest_begin(c, all, pertinent, index_seed, weight_seed, stream, out, PayloadWeights::INDEXED_LEN,
+                      "omr_digest_begin_indexed_len", payload_len);
 }
 
 extern "C" omr_status omr_digest_begin_seek(omr_ctx *c, size_t all, size_t pertinent, uint64_t index_seed,
@@ -352,6 +374,13 @@ extern "C" omr_status omr_digest_get_info(omr_digest *dg, omr_digest_info *info)
   info->all_payloads_count = dg->all;
   info->messages = dg->ranges.covered();
   info->pv_capacity_messages = dg->pv.capacity() / (2 * (size_t)N2);
+  return OMR_OK;
+}
+
+extern "C" omr_status omr_digest_get_payload_layout(omr_digest *dg, omr_payload_layout *layout) {
+  if (!dg || !layout) return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_digest_get_payload_layout: NULL argument");
+  std::lock_guard<std::mutex> lk(dg->mu);
+  *layout = dg->ly;
   return OMR_OK;
 }
 

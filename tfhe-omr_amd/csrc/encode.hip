@@ -1,7 +1,8 @@
 // Encode (detector.rs:223-453): the index and payload encode kernels' launches over the context's
 // partial-sum scratch, their reduction or accumulation, and the four encode entry points; the bitmap
 // digest's kernel (bitmap_kernel.hpp, none in the reference) the same way, with its two entry points;
-// the payload encode with indexed weights (none in the reference) and the device table of those weights;
+// the payload encode with indexed weights (none in the reference), at 612 words or at a length given by the
+// caller, and the device table of those weights;
 // the payload encode with the reference's weights by seek and the device builder of a seek.
 #include <algorithm>
 
@@ -88,6 +89,11 @@ omr_status omr::encode_payloads(omr_ctx *c, const uint64_t *pv, const uint16_t *
         encode_payloads_seek_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, all, w.key, w.seek, w.combos,
                                                             first_ct, (int)per_ct, per_wg, tw, partial);
         break;
+      case PayloadWeights::INDEXED_LEN:
+        encode_payloads_indexed_len_kernel<<<grid, ENC_T, 0, st>>>(pv, payloads, (int)D, offset, w.key, w.combos,
+                                                                   first_ct, (int)w.len, (int)per_ct,
+                                                                   (int)payload_stripes(w.len), per_wg, tw, partial);
+        break;
     }
   });
 }
@@ -148,11 +154,11 @@ omr_status encode_payloads_locked(omr_ctx *c, const uint64_t *pv, const uint16_t
   HIP_TRY(hipSetDevice(c->device));
   return encode_payloads(c, pv, payloads, D, offset, all, w, first_ct, n_ct, per_ct, out, (hipStream_t)stream, false);
 }
-// The host-buffer entries' common path: pv (and the payloads, when the entry has them) uploaded, run(d_pv,
-// d_payloads, d_out) = the device entry on c->stream, and its n_ct ciphertexts downloaded once it is done.
+// The host-buffer entries' common path: pv (and the payloads [D][len], when the entry has them) uploaded,
+// run(d_pv, d_payloads, d_out) = the device entry on c->stream, and its n_ct ciphertexts downloaded once it is done.
 template <typename Run>
 omr_status encode_from_host(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D, uint32_t n_ct,
-                            uint64_t *out, Run run) {
+                            uint64_t *out, Run run, size_t len = PAYLOAD_LEN) {
   HIP_TRY(hipSetDevice(c->device));
   DevBuf<uint64_t> dpv, dout;
   DevBuf<uint16_t> dpay;
@@ -160,8 +166,8 @@ omr_status encode_from_host(omr_ctx *c, const uint64_t *pv, const uint16_t *payl
   HIP_TRY(dout.alloc((size_t)n_ct * 2 * N2));
   HIP_TRY(hipMemcpy(dpv, pv, D * 2 * N2 * sizeof(uint64_t), hipMemcpyHostToDevice));
   if (payloads) {
-    HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * PAYLOAD_LEN));
-    HIP_TRY(hipMemcpy(dpay, payloads, D * PAYLOAD_LEN * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIP_TRY(dpay.alloc(std::max<size_t>(D, 1) * len));
+    HIP_TRY(hipMemcpy(dpay, payloads, D * len * sizeof(uint16_t), hipMemcpyHostToDevice));
   }
   OMR_TRY(run((const uint64_t *)dpv, (const uint16_t *)dpay, (uint64_t *)dout));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -241,6 +247,34 @@ extern "C" omr_status omr_encode_payloads_indexed(omr_ctx *c, const uint64_t *pv
                                               c->stream);
   };
   return encode_from_host(c, pv, payloads, D, n_ct, out, run);
+}
+
+extern "C" omr_status omr_encode_payloads_indexed_len_device(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads,
+                                                             size_t D, size_t offset, size_t all,
+                                                             const uint8_t seed[32], uint32_t combos, uint32_t len,
+                                                             uint32_t per_ct, uint32_t first_ct, uint32_t n_ct,
+                                                             uint64_t *out, void *stream) {
+  // the checks of check_payload_args, with the length's own bound on per_ct in place of per_ct * 612 <= 2048
+  if (!c || !out || !seed || (D && (!pv || !payloads)) || n_ct == 0 || n_ct > 65535 || !payload_len_ok(len) ||
+      per_ct == 0 || per_ct > payload_per_max(len) || !range_on_board(offset, D, all) || D > (size_t)INT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_indexed_len_device: bad argument");
+  PayloadWeights w;
+  w.kind = PayloadWeights::INDEXED_LEN, w.key = weight_key(seed), w.combos = combos, w.len = len;
+  return encode_payloads_locked(c, pv, payloads, D, offset, all, w, first_ct, n_ct, per_ct, out, stream);
+}
+
+extern "C" omr_status omr_encode_payloads_indexed_len(omr_ctx *c, const uint64_t *pv, const uint16_t *payloads, size_t D,
+                                                      size_t offset, size_t all, const uint8_t seed[32], uint32_t combos,
+                                                      uint32_t len, uint32_t per_ct, uint32_t first_ct, uint32_t n_ct,
+                                                      uint64_t *out) {
+  // what sizes the uploads is checked here; the device entry checks the rest before anything is enqueued
+  if (!c || !out || !seed || (D && (!pv || !payloads)) || n_ct == 0 || n_ct > 65535 || !payload_len_ok(len))
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_encode_payloads_indexed_len: bad argument");
+  auto run = [&](const uint64_t *dpv, const uint16_t *dpay, uint64_t *dout) {
+    return omr_encode_payloads_indexed_len_device(c, dpv, dpay, D, offset, all, seed, combos, len, per_ct, first_ct,
+                                                  n_ct, dout, c->stream);
+  };
+  return encode_from_host(c, pv, payloads, D, n_ct, out, run, len);
 }
 
 extern "C" omr_status omr_indexed_weights_table_device(const uint8_t seed[32], size_t all, uint32_t combos,

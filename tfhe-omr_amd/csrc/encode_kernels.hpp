@@ -138,6 +138,18 @@ struct TableWeights {
 constexpr int ENC_W_PER_CT = N2 / PAYLOAD_LEN;        // 3: the most combinations a ciphertext holds
 constexpr int ENC_W_BLOCKS = ENC_T / 16 + 1;          // 9
 static_assert(ENC_W_PER_CT * ENC_W_BLOCKS <= ENC_T, "one thread per staged weight block");
+// One staged block: combination `combo`'s weights for the 16 messages of block blk, zeros for padding. The
+// body of IndexedWeights::stage below, for encode_payloads_indexed_len_kernel's strided staging; stage keeps
+// its own text because calling this from it reordered encode_payloads_indexed_kernel's listing.
+__device__ __forceinline__ void indexed_weights_stage_block(const WeightKey &key, uint32_t combos, uint64_t combo,
+                                                            uint64_t blk, uint16_t *dst) {
+  if (combo < (uint64_t)combos) {
+    indexed_weight_block(key, (uint32_t)combo, blk, dst);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dst[i] = 0;
+  }
+}
 struct IndexedWeights {  // its kernel reads wts itself (see there): no ROUND, no weight()
   using Lds = uint16_t[ENC_W_PER_CT][ENC_W_BLOCKS * 16];
   Lds &wts;
@@ -153,6 +165,7 @@ struct IndexedWeights {  // its kernel reads wts itself (see there): no ROUND, n
     lane0 = (int)(g0 & 15);
     if (tid < per_ct * nblk) {
       const int j = tid / nblk, b = tid - j * nblk;
+      // the padding rule below is also indexed_weights_stage_block's (above): change the two together
       uint16_t *dst = &wts[j][b * 16];
       if (combo0 + j < (uint64_t)combos) {
         indexed_weight_block(key, (uint32_t)(combo0 + j), blk0 + b, dst);
@@ -306,6 +319,80 @@ __global__ __launch_bounds__(ENC_T) void encode_payloads_indexed_kernel(
           const int l = pos - j * PAYLOAD_LEN;
           const uint32_t w = wts[j][wi];
           v = centred_lift(((uint32_t)payloads[(size_t)m * PAYLOAD_LEN + l] * w) % (uint32_t)P);
+        }
+        x[e] = v;
+      }
+      encode_fold(pv + (size_t)m * 2 * N2, x, xch, tw, accA, accB);
+    }
+  }
+  encode_store(partial, accA, accB);
+}
+
+// The indexed payload encode with the payload length as an argument (include/omr_gpu.h, "Payload length as a
+// board parameter"): payloads [D][L] u16, 1 <= L <= OMR_PAYLOAD_LEN_MAX. Ciphertext ct = first_ct + blockIdx.y
+// is stripe ct % stripes of group ct / stripes, which holds the combinations (ct / stripes) * per_ct + j,
+// j < per_ct <= 16. One stripe: slot j * L + l is word l of combination j. Several stripes (per_ct = 1): slot i
+// is word N2 * stripe + i while that is below L. Every other slot is zero.
+//
+// A thread's ENC_E slots tid + ENC_T * e are the same for every message, so each is decoded once, before the
+// message loop, into one word: the combination's row offset in the staged weights (high half), the payload
+// word (low half), or ENC_LEN_ZERO. The loop itself has no division. The weights are IndexedWeights' blocks
+// for up to 16 combinations: 16 x 9 blocks are more than the ENC_T threads, so staging is a strided loop.
+constexpr int ENC_LEN_PER_CT = OMR_PAYLOAD_PER_CT_MAX;  // 16
+constexpr int ENC_LEN_ROW = ENC_W_BLOCKS * 16;          // 144 staged weights per combination
+constexpr uint32_t ENC_LEN_ZERO = 0xFFFFFFFFu;
+static_assert(ENC_LEN_PER_CT * ENC_LEN_ROW < 65536 && OMR_PAYLOAD_LEN_MAX <= 65536, "a slot decodes to two u16 halves");
+static_assert(OMR_PAYLOAD_LEN_MAX <= 8 * N2, "at most 8 stripes");
+__global__ __launch_bounds__(ENC_T) void encode_payloads_indexed_len_kernel(
+    const uint64_t *__restrict__ pv, const uint16_t *__restrict__ payloads, int D, uint64_t offset,
+    WeightKey key, uint32_t combos, uint32_t first_ct, int L, int per_ct, int stripes, int per_wg,
+    const double *__restrict__ tw, uint64_t *__restrict__ partial) {
+  __shared__ double xch[EncNtt::LDS_DOUBLES];
+  __shared__ uint16_t wts[ENC_LEN_PER_CT * ENC_LEN_ROW];
+  const int tid = threadIdx.x;
+  const uint64_t ct = (uint64_t)first_ct + blockIdx.y;
+  const uint64_t combo0 = ct / (uint32_t)stripes * (uint32_t)per_ct;
+  const int word0 = (int)(ct % (uint32_t)stripes) * N2;  // the stripe's first payload word
+  uint32_t at[ENC_E];
+#pragma unroll
+  for (int e = 0; e < ENC_E; ++e) {
+    const int pos = tid + e * ENC_T;
+    if (stripes == 1) {
+      const int j = pos / L;
+      at[e] = j < per_ct ? (uint32_t)(j * ENC_LEN_ROW) << 16 | (uint32_t)(pos - j * L) : ENC_LEN_ZERO;
+    } else {
+      at[e] = word0 + pos < L ? (uint32_t)(word0 + pos) : ENC_LEN_ZERO;
+    }
+  }
+  const int m0 = blockIdx.x * per_wg;
+  const int mcount = min(per_wg, D - m0);
+  double accA[ENC_E], accB[ENC_E];
+  encode_init(accA, accB);
+#pragma unroll 1
+  for (int mb = 0; mb < mcount; mb += ENC_T) {
+    const int cnt = min(ENC_T, mcount - mb);
+    const uint64_t g0 = offset + m0 + mb, blk0 = g0 >> 4;
+    const int nblk = (int)(((g0 + cnt - 1) >> 4) - blk0) + 1;  // <= ENC_W_BLOCKS
+    const int lane0 = (int)(g0 & 15);
+    __syncthreads();  // every thread has finished reading the previous round's weights
+#pragma unroll 1
+    for (int t = tid; t < per_ct * nblk; t += ENC_T) {
+      const int j = t / nblk, b = t - j * nblk;
+      indexed_weights_stage_block(key, combos, combo0 + j, blk0 + b, &wts[j * ENC_LEN_ROW + b * 16]);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int mi = mb; mi < mb + cnt; ++mi) {
+      const int m = m0 + mi;
+      const int wi = lane0 + (mi - mb);
+      const uint16_t *__restrict__ pay = payloads + (size_t)m * L;
+      double x[ENC_E];
+#pragma unroll
+      for (int e = 0; e < ENC_E; ++e) {
+        double v = 0.0;
+        if (at[e] != ENC_LEN_ZERO) {
+          const uint32_t w = wts[(at[e] >> 16) + wi];
+          v = centred_lift(((uint32_t)pay[at[e] & 0xFFFFu] * w) % (uint32_t)P);
         }
         x[e] = v;
       }

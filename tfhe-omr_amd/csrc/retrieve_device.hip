@@ -181,9 +181,10 @@ omr_status indices_locked(omr_auditor *aud, const void *idx_cts, uint32_t n_ct, 
 // the device, so with a row cap; a NULL seek is built on the auditor's device.
 omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits, size_t all,
                            uint32_t combination_count, const MatrixSource &src, const size_t *indices,
-                           size_t n_indices, uint16_t *payloads, omr_audit_summary *summary, const std::string &who) {
+                           size_t n_indices, uint16_t *payloads, omr_audit_summary *summary, const std::string &who,
+                           const omr_payload_layout *ly = nullptr) {
   PayloadSystem sys;
-  OMR_TRY(payload_system(all, combination_count, n_ct, indices, n_indices, who, &sys));
+  OMR_TRY(payload_system(all, combination_count, n_ct, indices, n_indices, who, &sys, ly));
   if (sys.cols == 0) return OMR_OK;
   const size_t rows = sys.rows, cols = sys.cols;
   if (rows > OMR_SOLVE_MAX_ROWS)
@@ -200,8 +201,9 @@ omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
   OMR_TRY(decode_cts(aud, pay_cts, n_ct, bits, summary, who.c_str()));
   // the stream is idle here (the decode ends with a synchronisation), so growing is safe
   HIP_TRY(r.matrix.reserve(rows * cols));
-  HIP_TRY(r.rhs.reserve(rows * PAYLOAD_LEN));
-  HIP_TRY(r.solution.reserve(cols * PAYLOAD_LEN));
+  const size_t len = sys.len;
+  HIP_TRY(r.rhs.reserve(rows * len));
+  HIP_TRY(r.solution.reserve(cols * len));
   HIP_TRY(r.status.reserve(1));
   std::vector<uint16_t> h_m;
   std::vector<uint64_t> h_idx;
@@ -221,12 +223,16 @@ omr_status payloads_locked(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
       retrieve_matrix_kernel<<<col_grid(rows * cols), SOLVE_COL_T, 0, st>>>(key, r.indices, (uint32_t)rows, (uint32_t)cols,
                                                                             r.matrix);
   }
-  retrieve_rhs_kernel<<<col_grid(rows * PAYLOAD_LEN), SOLVE_COL_T, 0, st>>>(r.decoded, (uint32_t)rows, (uint32_t)sys.per,
-                                                                            r.rhs);
+  if (ly)
+    retrieve_rhs_len_kernel<<<col_grid(rows * len), SOLVE_COL_T, 0, st>>>(r.decoded, (uint32_t)rows, (uint32_t)sys.per,
+                                                                          (uint32_t)len, (uint32_t)sys.stripes, r.rhs);
+  else
+    retrieve_rhs_kernel<<<col_grid(rows * PAYLOAD_LEN), SOLVE_COL_T, 0, st>>>(r.decoded, (uint32_t)rows, (uint32_t)sys.per,
+                                                                              r.rhs);
   omr_status s = hipGetLastError() == hipSuccess ? OMR_OK : set_error(OMR_ERR_DEVICE, who + ": kernel launch failed");
-  if (s == OMR_OK) s = launch_solve(aud, r.matrix, r.rhs, rows, cols, PAYLOAD_LEN, r.solution, r.status, st);
+  if (s == OMR_OK) s = launch_solve(aud, r.matrix, r.rhs, rows, cols, len, r.solution, r.status, st);
   uint32_t status = 0;
-  std::vector<uint16_t> sol(cols * PAYLOAD_LEN);
+  std::vector<uint16_t> sol(cols * len);
   hipError_t e = hipSuccess;
   if (s == OMR_OK) e = hipMemcpyAsync(&status, r.status, sizeof status, hipMemcpyDeviceToHost, st);
   if (s == OMR_OK && e == hipSuccess)
@@ -253,11 +259,12 @@ omr_status with_auditor(omr_auditor *aud, int bits, const std::string &who, Body
 // The three omr_auditor_retrieve_payloads* entries: they differ in where the matrix comes from.
 omr_status auditor_payloads(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits, size_t all,
                             uint32_t combination_count, const MatrixSource &src, const size_t *indices, size_t n_indices,
-                            uint16_t *payloads, const std::string &who) {
+                            uint16_t *payloads, const std::string &who, const omr_payload_layout *ly = nullptr) {
   if (!retrieve_args_ok(aud, pay_cts, src, indices, n_indices, payloads))
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
   return with_auditor(aud, bits, who, [&] {
-    return payloads_locked(aud, pay_cts, n_ct, bits, all, combination_count, src, indices, n_indices, payloads, nullptr, who);
+    return payloads_locked(aud, pay_cts, n_ct, bits, all, combination_count, src, indices, n_indices, payloads, nullptr, who,
+                           ly);
   });
 }
 
@@ -291,6 +298,17 @@ extern "C" omr_status omr_auditor_retrieve_payloads_indexed(omr_auditor *aud, co
   return auditor_payloads(aud, pay_cts, n_ct, bits, all_payloads_count, combination_count,
                           MatrixSource{nullptr, weight_seed}, indices, n_indices, payloads,
                           "omr_auditor_retrieve_payloads_indexed");
+}
+
+extern "C" omr_status omr_auditor_retrieve_payloads_indexed_len(omr_auditor *aud, const void *pay_cts, uint32_t n_ct,
+                                                                int bits, size_t all_payloads_count,
+                                                                const omr_payload_layout *layout,
+                                                                const uint8_t weight_seed[32], const size_t *indices,
+                                                                size_t n_indices, uint16_t *payloads) {
+  const char *who = "omr_auditor_retrieve_payloads_indexed_len";
+  if (!layout) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  return auditor_payloads(aud, pay_cts, n_ct, bits, all_payloads_count, layout->combination_count,
+                          MatrixSource{nullptr, weight_seed}, indices, n_indices, payloads, who, layout);
 }
 
 extern "C" omr_status omr_auditor_retrieve_payloads_seek(omr_auditor *aud, const void *pay_cts, uint32_t n_ct, int bits,

@@ -35,20 +35,32 @@ inline void write_indices(const std::set<size_t> &set, size_t *indices, size_t c
   }
 }
 
-// The system of a payload retrieval: rows combinations in cols unknowns, `per` combinations per ciphertext.
+// The system of a payload retrieval: rows combinations in cols unknowns of `len` words each, `per` combinations
+// per group of `stripes` ciphertexts (612 words and one stripe unless the entry takes a layout).
 struct PayloadSystem {
-  size_t rows = 0, cols = 0, per = 0;
+  size_t rows = 0, cols = 0, per = 0, len = PAYLOAD_LEN, stripes = 1;
 };
 // The checks of every payload entry after its NULL test. cols = 0 (no index) is no error: nothing to solve.
+// `ly` is the layout of an *_indexed_len entry (its combination_count, then, is the system's), NULL otherwise.
 inline omr_status payload_system(size_t all, uint32_t combination_count, uint32_t n_ct, const size_t *indices,
-                                 size_t n_indices, const std::string &who, PayloadSystem *sys) {
+                                 size_t n_indices, const std::string &who, PayloadSystem *sys,
+                                 const omr_payload_layout *ly = nullptr) {
   omr_retrieval_params rp;
   OMR_TRY(omr_get_retrieval_params(all, n_indices, &rp));
   sys->rows = combination_count ? combination_count : rp.combination_count;
   sys->cols = n_indices;
   sys->per = rp.cmb_count_per_cipher;
+  if (ly) {
+    if (!payload_len_ok(ly->payload_len) || ly->cmb_count_per_cipher == 0 ||
+        ly->cmb_count_per_cipher > payload_per_max(ly->payload_len))
+      return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": a payload length or combinations per ciphertext out of range");
+    sys->rows = ly->combination_count;
+    sys->per = ly->cmb_count_per_cipher;
+    sys->len = ly->payload_len;
+    sys->stripes = payload_stripes(ly->payload_len);
+  }
   if (n_indices == 0) return OMR_OK;
-  if ((size_t)n_ct * sys->per < sys->rows)
+  if ((size_t)n_ct / sys->stripes * sys->per < sys->rows)  // whole groups only
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": too few payload ciphertexts");
   if (sys->rows < sys->cols)  // matrix.rs:171 asserts num_rows >= num_cols
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": fewer combinations than indices");
@@ -75,6 +87,16 @@ inline omr_status fill_matrix_host(const MatrixSource &src, const omr_weight_see
   for (size_t j = 0; j < sys.rows; ++j)
     for (size_t k = 0; k < sys.cols; ++k) m[j * sys.cols + k] = src.weights[j * all + indices[k]];
   return OMR_OK;
+}
+
+// The system's right-hand side from the decoded payload ciphertexts [n_ct][N2] (decode_combined_payloads,
+// retriever.rs:318-362, for any layout): rhs[j][l] = word l of combination j (weights.hpp, payload_word_at).
+template <typename T>
+void gather_rhs_host(const T *dec, const PayloadSystem &sys, uint16_t *rhs) {
+  for (size_t j = 0; j < sys.rows; ++j)
+    for (size_t l = 0; l < sys.len; ++l)
+      rhs[j * sys.len + l] = (uint16_t)dec[payload_word_at((uint32_t)j, (uint32_t)l, (uint32_t)sys.len, (uint32_t)sys.per,
+                                                           (uint32_t)sys.stripes)];
 }
 
 // The NULL test of the payload entries: `owner` is the secret key pack or the auditor.

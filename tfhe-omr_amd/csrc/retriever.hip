@@ -176,11 +176,12 @@ omr_status solve_mod257(const uint16_t *matrix, const uint16_t *rhs, size_t rows
 // system's matrix comes from (retrieve_system.hpp). No row cap: the solve is this file's, on this thread.
 omr_status retrieve_payloads_body(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct, size_t all,
                                   uint32_t combination_count, const MatrixSource &src, const size_t *indices,
-                                  size_t n_indices, uint16_t *payloads, const std::string &who) {
+                                  size_t n_indices, uint16_t *payloads, const std::string &who,
+                                  const omr_payload_layout *ly = nullptr) {
   if (!retrieve_args_ok(sk, pay_cts, src, indices, n_indices, payloads))
     return set_error(OMR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
   PayloadSystem sys;
-  OMR_TRY(payload_system(all, combination_count, n_ct, indices, n_indices, who, &sys));
+  OMR_TRY(payload_system(all, combination_count, n_ct, indices, n_indices, who, &sys, ly));
   if (sys.cols == 0) return OMR_OK;
   omr_weight_seek seek{};
   if (src.by_seek)
@@ -189,17 +190,16 @@ omr_status retrieve_payloads_body(const omr_secret_key_pack *sk, const uint64_t 
                            return omr_weight_seek_build_cpu(seed, draws, 0, out);
                          },
                          &seek));
-  // decode_combined_payloads: combination j lives in ciphertext j / per, slots (j % per) * 612..
-  std::vector<uint16_t> rhs(sys.rows * PAYLOAD_LEN);
+  // decode_combined_payloads: combination j lives in ciphertext j / per, slots (j % per) * 612.. (a layout
+  // with a length of its own: retrieve_system.hpp, gather_rhs_host)
+  std::vector<uint16_t> rhs(sys.rows * sys.len);
   std::vector<uint32_t> dec((size_t)n_ct * N2);
   parallel_for(n_ct, 0, [&](size_t c) { decrypt_decode_one(sk, pay_cts + c * 2 * N2, P, &dec[c * N2]); });
-  for (size_t j = 0; j < sys.rows; ++j)
-    for (int b = 0; b < PAYLOAD_LEN; ++b)
-      rhs[j * PAYLOAD_LEN + b] = (uint16_t)dec[(j / sys.per) * N2 + (j % sys.per) * PAYLOAD_LEN + b];
+  gather_rhs_host(dec.data(), sys, rhs.data());
   std::vector<uint16_t> m(sys.rows * sys.cols);
   OMR_TRY(fill_matrix_host(src, seek, sys, all, indices, m.data()));
   // forward elimination with the first non-zero pivot, then back substitution (matrix.rs), on this thread
-  return solve_mod257(m.data(), rhs.data(), sys.rows, sys.cols, PAYLOAD_LEN, payloads, nullptr, 1);
+  return solve_mod257(m.data(), rhs.data(), sys.rows, sys.cols, sys.len, payloads, nullptr, 1);
 }
 
 }  // namespace
@@ -220,6 +220,16 @@ extern "C" omr_status omr_retrieve_payloads_indexed(const omr_secret_key_pack *s
   return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, combination_count,
                                 MatrixSource{nullptr, weight_seed}, indices, n_indices, payloads,
                                 "omr_retrieve_payloads_indexed");
+}
+
+extern "C" omr_status omr_retrieve_payloads_indexed_len(const omr_secret_key_pack *sk, const uint64_t *pay_cts,
+                                                        uint32_t n_ct, size_t all_payloads_count,
+                                                        const omr_payload_layout *layout, const uint8_t weight_seed[32],
+                                                        const size_t *indices, size_t n_indices, uint16_t *payloads) {
+  const char *who = "omr_retrieve_payloads_indexed_len";
+  if (!layout) return set_error(OMR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  return retrieve_payloads_body(sk, pay_cts, n_ct, all_payloads_count, layout->combination_count,
+                                MatrixSource{nullptr, weight_seed}, indices, n_indices, payloads, who, layout);
 }
 
 extern "C" omr_status omr_retrieve_payloads_seek(const omr_secret_key_pack *sk, const uint64_t *pay_cts, uint32_t n_ct,

@@ -324,4 +324,14 @@ retrieve_rhs_kernel(const uint16_t *__restrict__ decoded, uint32_t rows, uint32_
   rhs[idx] = decoded[(size_t)(j / per) * N2 + (j % per) * PAYLOAD_LEN + b];
 }
 
+// The same for a layout with a payload length of its own (weights.hpp, payload_word_at): combination j's L
+// words gathered across the `stripes` ciphertexts of its group; rhs [rows][L].
+__global__ void __launch_bounds__(SOLVE_COL_T)
+retrieve_rhs_len_kernel(const uint16_t *__restrict__ decoded, uint32_t rows, uint32_t per, uint32_t L, uint32_t stripes,
+                        uint16_t *__restrict__ rhs) {
+  const size_t idx = (size_t)blockIdx.x * SOLVE_COL_T + threadIdx.x;
+  if (idx >= (size_t)rows * L) return;
+  rhs[idx] = decoded[payload_word_at((uint32_t)(idx / L), (uint32_t)(idx % L), L, per, stripes)];
+}
+
 }  // namespace omr

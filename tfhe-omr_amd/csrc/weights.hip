@@ -37,6 +37,21 @@ extern "C" omr_status omr_get_retrieval_params(size_t all, size_t pertinent,
   return OMR_OK;
 }
 
+extern "C" omr_status omr_get_payload_layout(size_t pertinent, size_t payload_len, omr_payload_layout *ly) {
+  if (!ly || !payload_len_ok(payload_len) || pertinent > (size_t)UINT32_MAX - 5)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_get_payload_layout: NULL, or a length or count out of range");
+  const uint32_t L = (uint32_t)payload_len;
+  ly->payload_len = L;
+  ly->combination_count = (uint32_t)pertinent + 5;  // as omr_get_retrieval_params
+  ly->cmb_count_per_cipher = payload_per_max(L);
+  ly->stripes = payload_stripes(L);
+  const uint64_t groups = ((uint64_t)ly->combination_count + ly->cmb_count_per_cipher - 1) / ly->cmb_count_per_cipher;
+  if (groups * ly->stripes > UINT32_MAX)
+    return set_error(OMR_ERR_INVALID_ARGUMENT, "omr_get_payload_layout: more than 2^32 payload ciphertexts");
+  ly->payload_ct = (uint32_t)(groups * ly->stripes);
+  return OMR_OK;
+}
+
 extern "C" omr_status omr_payload_weights(const uint8_t seed[32], size_t all, uint32_t combos,
                                           uint32_t n_ct, uint32_t per_ct, uint16_t *out) {
   if (!seed || !out || (size_t)n_ct * per_ct < combos)

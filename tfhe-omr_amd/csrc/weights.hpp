@@ -34,6 +34,23 @@ OMR_HD void indexed_weight_block(const WeightKey &key, uint32_t j, uint64_t bloc
   for (int i = 0; i < 16; ++i) out[i] = (uint16_t)(((uint64_t)w[i] * (uint64_t)P) >> 32);
 }
 
+// Payload length as a board parameter (include/omr_gpu.h): a payload of L words, 1 <= L <= OMR_PAYLOAD_LEN_MAX,
+// takes payload_stripes(L) ciphertexts per group of at most payload_per_max(L) combinations. The layout
+// function, the encode entry, the session and both retrievals share these.
+inline bool payload_len_ok(size_t L) { return L >= 1 && L <= OMR_PAYLOAD_LEN_MAX; }
+OMR_HD uint32_t payload_stripes(uint32_t L) { return (L + N2 - 1) / N2; }
+OMR_HD uint32_t payload_per_max(uint32_t L) {
+  if (L > (uint32_t)N2) return 1;
+  const uint32_t fit = (uint32_t)N2 / L;
+  return fit < OMR_PAYLOAD_PER_CT_MAX ? fit : OMR_PAYLOAD_PER_CT_MAX;
+}
+// Where word l < L of combination j lies among the decoded payload ciphertexts u16 [n_ct][N2]: group j / per,
+// stripe l / N2; within a one-stripe ciphertext combination j % per starts at slot (j % per) * L (several
+// stripes have per = 1, so that term is 0).
+OMR_HD size_t payload_word_at(uint32_t j, uint32_t l, uint32_t L, uint32_t per, uint32_t stripes) {
+  return ((size_t)(j / per) * stripes + l / (uint32_t)N2) * N2 + (size_t)(j % per) * L + l % (uint32_t)N2;
+}
+
 // Reference payload weights by seek (include/omr_gpu.h, "Reference payload weights by seek"): the
 // statement that the builders, omr_payload_weights_at, the seek encode kernel and the auditor's matrix
 // kernel share. The stream is omr_payload_weights': ChaCha12, stream id 0, raw position r = word r & 15

@@ -5,7 +5,7 @@
 // indices and their payloads come back.
 //
 //   omr_e2e [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] [--seeded]
-//           [--compact BITS] [--audit-key] [--indexed-weights] [--seek-weights] [--device-retrieve]
+//           [--compact BITS] [--audit-key] [--indexed-weights] [--payload-len L] [--seek-weights] [--device-retrieve]
 //           [--sender] [--host-only]
 //
 // --session PIECE runs the same board through a digest session (omr_digest_*) in host pieces of
@@ -37,6 +37,11 @@
 // the detector encodes with omr_encode_payloads_indexed (or a session from omr_digest_begin_indexed) and the
 // recipient solves with omr_retrieve_payloads_indexed; nobody draws the board-wide weight table. With
 // --host-only it checks omr_indexed_weights_at against omr_indexed_weights_table on the pertinent set.
+// --payload-len L (with --indexed-weights) makes the payload length a parameter of the board (include/omr_gpu.h,
+// "Payload length as a board parameter"): payloads of L words, 1 <= L <= 16384, in omr_get_payload_layout's
+// ciphertexts; the detector encodes with omr_encode_payloads_indexed_len (or a session from
+// omr_digest_begin_indexed_len) and the recipient solves with omr_retrieve_payloads_indexed_len (with
+// --device-retrieve: omr_auditor_retrieve_payloads_indexed_len). Works with --session, --compact, --bitmap.
 // --seek-weights keeps the reference's weights and drops the table (include/omr_gpu.h, "Reference payload weights
 // by seek"): the detector builds the seek of the board on its device and encodes with omr_encode_payloads_seek
 // (or a session from omr_digest_begin_seek), the recipient solves with omr_retrieve_payloads_seek, which builds its
@@ -90,6 +95,8 @@ int main(int argc, char **argv) {
   size_t session_piece = 0;  // --session: messages per omr_digest_update call
   bool audit = false, bitmap = false, seeded = false, audit_key = false, indexed = false, seek_weights = false, device_retrieve = false, sender = false;
   int compact_bits = 0;  // --compact: bits per coefficient of the digest on the wire
+  bool by_len = false;     // --payload-len given: the payload length is a parameter of the (indexed) board
+  size_t payload_len = 0;  // its words per payload, 1 .. OMR_PAYLOAD_LEN_MAX
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if ((a == "-p" || a == "--payload-count") && i + 1 < argc) D = std::max<size_t>(1, std::stoull(argv[++i]));
@@ -102,17 +109,32 @@ int main(int argc, char **argv) {
     else if (a == "--compact" && i + 1 < argc) compact_bits = std::atoi(argv[++i]);
     else if (a == "--audit-key") audit_key = true;
     else if (a == "--indexed-weights") indexed = true;
+    else if (a == "--payload-len" && i + 1 < argc) {
+      // digits only (stoull would take a sign and wrap it), and in the library's range: 0 is no length
+      const std::string v = argv[++i];
+      const bool digits = !v.empty() && v.size() <= 5 && v.find_first_not_of("0123456789") == std::string::npos;
+      payload_len = digits ? std::stoull(v) : 0;
+      if (payload_len < 1 || payload_len > OMR_PAYLOAD_LEN_MAX) {
+        std::fprintf(stderr, "--payload-len takes a length of 1 to %d words, not '%s'\n", OMR_PAYLOAD_LEN_MAX, v.c_str());
+        return 2;
+      }
+      by_len = true;
+    }
     else if (a == "--seek-weights") seek_weights = true;
     else if (a == "--device-retrieve") device_retrieve = true;
     else if (a == "--sender") sender = true;
     else if (a == "--host-only") host_only = true;
     else {
       std::fprintf(stderr, "usage: %s [-p payload_count] [-d device] [-s seed] [--session PIECE] [--audit] [--bitmap] "
-                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--seek-weights] "
+                   "[--seeded] [--compact BITS] [--audit-key] [--indexed-weights] [--payload-len L] [--seek-weights] "
                    "[--device-retrieve] [--sender] [--host-only]\n",
                    argv[0]);
       return 2;
     }
+  }
+  if (by_len && !indexed) {
+    std::fprintf(stderr, "--payload-len needs --indexed-weights: the table and seek conventions stay at 612 words\n");
+    return 2;
   }
   std::printf("%s; all payloads count: %zu\n", omr_version(), D);
 
@@ -216,12 +238,17 @@ int main(int argc, char **argv) {
     std::printf("gen clues time: %.3f s\n", secs(t));
   }
 
-  // Payload::random (omr.rs:140-146)
-  std::vector<uint16_t> payloads(D * PAYLOAD);
-  for (auto &b : payloads) b = (uint16_t)(rng() & 0xff);
-
   omr_retrieval_params rp;
   CHECK(omr_get_retrieval_params(D, pert_count, &rp));
+  // the payload digest's layout: the reference's (2 combinations of 612 words per ciphertext) or the length's own
+  omr_payload_layout ly{(uint32_t)PAYLOAD, rp.combination_count, rp.cmb_count_per_cipher, 1, rp.cmb_cipher_count};
+  if (by_len) CHECK(omr_get_payload_layout(pert_count, payload_len, &ly));
+  const size_t plen = ly.payload_len;
+
+  // Payload::random (omr.rs:140-146)
+  std::vector<uint16_t> payloads(D * plen);
+  for (auto &b : payloads) b = (uint16_t)(rng() & 0xff);
+
   uint8_t wseed[32];
   for (int i = 0; i < 32; ++i) wseed[i] = (uint8_t)(rng() & 0xff);
   if (indexed && seek_weights) {
@@ -235,7 +262,10 @@ int main(int argc, char **argv) {
     CHECK(omr_payload_weights(wseed, D, rp.combination_count, rp.cmb_cipher_count, rp.cmb_count_per_cipher,
                               weights.data()));
   std::printf("retrieval params: %u index ct, %u payload ct (%u combinations)\n",
-              rp.max_encode_indices_cipher_count, rp.cmb_cipher_count, rp.combination_count);
+              rp.max_encode_indices_cipher_count, ly.payload_ct, rp.combination_count);
+  if (by_len)
+    std::printf("payload layout: %u words, %u combinations per ciphertext, %u stripes\n", ly.payload_len,
+                ly.cmb_count_per_cipher, ly.stripes);
   uint32_t n_bmp = 0;
   if (bitmap) CHECK(omr_bitmap_ct_count(D, &n_bmp));
   if (host_only && bitmap) {
@@ -340,7 +370,7 @@ int main(int argc, char **argv) {
   if (seeded) CHECK(omr_ctx_create_seeded(&sview, device, &ctx));
   else CHECK(omr_ctx_create(&view, device, &ctx));
   std::printf("detector creation time: %.3f s (%s)\n", secs(t), seeded ? "seeded key, expanded on the device" : "full key");
-  const uint32_t n_idx = rp.max_encode_indices_cipher_count, n_pay = rp.cmb_cipher_count;
+  const uint32_t n_idx = rp.max_encode_indices_cipher_count, n_pay = ly.payload_ct;
   omr_auditor *aud = nullptr;
   if (audit) CHECK(omr_auditor_create(pa, device, &aud));
   int audit_fails = 0;
@@ -353,13 +383,14 @@ int main(int argc, char **argv) {
     // the same flow inside the library, piece by piece (omr_digest_*): detect + both encoders
     t = clk::now();
     omr_digest *dg = nullptr;
-    if (indexed) CHECK(omr_digest_begin_indexed(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
+    if (by_len) CHECK(omr_digest_begin_indexed_len(ctx, D, pert_count, seed + 3, wseed, payload_len, nullptr, &dg));
+    else if (indexed) CHECK(omr_digest_begin_indexed(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
     else if (seek_weights) CHECK(omr_digest_begin_seek(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
     else CHECK(omr_digest_begin(ctx, D, pert_count, seed + 3, wseed, nullptr, &dg));
     if (bitmap) CHECK(omr_digest_enable_bitmap(dg));
     for (size_t off = 0; off < D; off += session_piece) {
       const size_t n = std::min(session_piece, D - off);
-      CHECK(omr_digest_update(dg, &ca[off * N0], &cb[off * CLUES], &payloads[off * PAYLOAD], n, off));
+      CHECK(omr_digest_update(dg, &ca[off * N0], &cb[off * CLUES], &payloads[off * plen], n, off));
     }
     CHECK(omr_digest_read(dg, idx_ct.data(), pay_ct.data()));
     if (bitmap) CHECK(omr_digest_read_bitmap(dg, bmp_ct.data()));
@@ -402,7 +433,10 @@ int main(int argc, char **argv) {
       CHECK(omr_encode_indices(ctx, pv.data(), D, 0, D, seed + 3, c, &idx_ct[(size_t)c * 2 * N2]));
     std::printf("encode indices time: %.3f s\n", secs(t));
     t = clk::now();
-    if (indexed) {
+    if (by_len) {
+      CHECK(omr_encode_payloads_indexed_len(ctx, pv.data(), payloads.data(), D, 0, D, wseed, ly.combination_count,
+                                            ly.payload_len, ly.cmb_count_per_cipher, 0, n_pay, pay_ct.data()));
+    } else if (indexed) {
       CHECK(omr_encode_payloads_indexed(ctx, pv.data(), payloads.data(), D, 0, D, wseed, rp.combination_count, 0, n_pay,
                                         rp.cmb_count_per_cipher, pay_ct.data()));
     } else if (seek_weights) {
@@ -500,8 +534,14 @@ int main(int argc, char **argv) {
     CHECK(omr_retrieve_indices(pa, idx_ct.data(), n_idx, D, pert_count, found.data(), found.size(), &nfound));
   }
   found.resize(std::min(nfound, found.size()));
-  std::vector<uint16_t> solved(found.size() * PAYLOAD);
-  if (device_retrieve && indexed)
+  std::vector<uint16_t> solved(found.size() * plen);
+  if (by_len && device_retrieve)
+    CHECK(omr_auditor_retrieve_payloads_indexed_len(ra, dev_pay, n_pay, compact_bits, D, &ly, wseed, found.data(),
+                                                    found.size(), solved.data()));
+  else if (by_len)
+    CHECK(omr_retrieve_payloads_indexed_len(pa, pay_ct.data(), n_pay, D, &ly, wseed, found.data(), found.size(),
+                                            solved.data()));
+  else if (device_retrieve && indexed)
     CHECK(omr_auditor_retrieve_payloads_indexed(ra, dev_pay, n_pay, compact_bits, D, rp.combination_count, wseed,
                                                 found.data(), found.size(), solved.data()));
   else if (device_retrieve && seek_weights)
@@ -525,7 +565,7 @@ int main(int argc, char **argv) {
   int fails = (found == pert ? 0 : 1) + audit_fails + compact_fails;
   if (fails) std::printf("Fail: %zu indices recovered, %zu pertinent\n", found.size(), pert.size());
   for (size_t k = 0; k < found.size() && !fails; ++k)
-    if (!std::equal(&solved[k * PAYLOAD], &solved[(k + 1) * PAYLOAD], &payloads[found[k] * PAYLOAD])) {
+    if (!std::equal(&solved[k * plen], &solved[(k + 1) * plen], &payloads[found[k] * plen])) {
       std::printf("Fail %zu\n", found[k]);
       ++fails;
     }

@@ -75,6 +75,12 @@ class _DigestInfo(C.Structure):
                 ("pv_capacity_messages", C.c_size_t)]
 
 
+class _PayloadLayout(C.Structure):
+    """omr_payload_layout."""
+    _fields_ = [(n, C.c_uint32) for n in ("payload_len", "combination_count", "cmb_count_per_cipher", "stripes",
+                                          "payload_ct")]
+
+
 class _AuditSummary(C.Structure):
     """omr_audit_summary."""
     _fields_ = [(n, C.c_uint64) for n in ("ciphertexts", "zero", "one_hot", "other", "max_abs_residual")] + \
@@ -287,6 +293,23 @@ EXPORTS = {
     "omr_auditor_retrieve_payloads_seek": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_size_t,
                                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                      C.c_void_p]),
+    # payload length as a board parameter (include/omr_gpu.h)
+    "omr_get_payload_layout": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(_PayloadLayout)]),
+    "omr_encode_payloads_indexed_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                  C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, C.c_void_p]),
+    "omr_encode_payloads_indexed_len_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                         C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                         C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "omr_digest_begin_indexed_len": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
+                                               C.c_void_p, C.POINTER(C.c_void_p)]),
+    "omr_digest_get_payload_layout": (C.c_int, [C.c_void_p, C.POINTER(_PayloadLayout)]),
+    "omr_retrieve_payloads_indexed_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t,
+                                                    C.POINTER(_PayloadLayout), C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]),
+    "omr_auditor_retrieve_payloads_indexed_len": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_size_t,
+                                                            C.POINTER(_PayloadLayout), C.c_void_p, C.c_void_p,
+                                                            C.c_size_t, C.c_void_p]),
 }
 
 _lib = None
@@ -333,6 +356,37 @@ class RetrievalParams:
                "omr_get_retrieval_params")
         for n, _ in _RetrievalParams._fields_:
             setattr(self, n, getattr(rp, n))
+
+
+PAYLOAD_LEN_MAX = 16384     # OMR_PAYLOAD_LEN_MAX
+PAYLOAD_PER_CT_MAX = 16     # OMR_PAYLOAD_PER_CT_MAX
+
+
+@dataclass
+class PayloadLayout:
+    """omr_payload_layout: the payload digest of a board whose payloads are payload_len words long
+    (include/omr_gpu.h, "Payload length as a board parameter"). PayloadLayout.of() asks the library; the
+    fields may be set by hand for a digest encoded with fewer combinations per ciphertext."""
+    payload_len: int
+    combination_count: int
+    cmb_count_per_cipher: int
+    stripes: int
+    payload_ct: int
+
+    @classmethod
+    def of(cls, pertinent_count: int, payload_len: int) -> "PayloadLayout":
+        t = _PayloadLayout()
+        _check(lib().omr_get_payload_layout(pertinent_count, payload_len, C.byref(t)), "omr_get_payload_layout")
+        return cls(**{n: getattr(t, n) for n, _ in _PayloadLayout._fields_})
+
+    def _struct(self) -> "_PayloadLayout":
+        return _PayloadLayout(self.payload_len, self.combination_count, self.cmb_count_per_cipher, self.stripes,
+                              self.payload_ct)
+
+
+def _layout_ref(layout):
+    """A PayloadLayout as the C struct by reference; None passes NULL."""
+    return None if layout is None else C.byref(layout._struct())
 
 
 def payload_weights(seed: bytes, rp: RetrievalParams) -> np.ndarray:
@@ -893,6 +947,19 @@ class Retriever:
                "omr_retrieve_payloads_indexed")
         return out
 
+    def decode_combined_payloads_and_solve_indexed_len(self, pay_cts, seed: bytes, indices,
+                                                       layout: "PayloadLayout") -> np.ndarray:
+        """omr_retrieve_payloads_indexed_len: u16 [len(indices)][layout.payload_len] from a digest of `layout`."""
+        cts = np.ascontiguousarray(pay_cts, dtype=np.uint64).reshape(-1, 2, N2)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        out = np.zeros((len(idx), layout.payload_len if layout else 0), np.uint16)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_retrieve_payloads_indexed_len(self._sk._h, cts.ctypes.data, cts.shape[0],
+                                                       self.params.all_payloads_count, _layout_ref(layout), ptr,
+                                                       idx.ctypes.data, len(idx), out.ctypes.data),
+               "omr_retrieve_payloads_indexed_len")
+        return out
+
     def decode_combined_payloads_and_solve_seek(self, pay_cts, seed: bytes, indices, seek: "WeightSeek" = None,
                                                 combination_count: int = None) -> np.ndarray:
         """omr_retrieve_payloads_seek: the solve of decode_combined_payloads_and_solve, the matrix taken from
@@ -1291,6 +1358,20 @@ class Auditor:
                                                            out.ctypes.data), "omr_auditor_retrieve_payloads_indexed")
         return out
 
+    def retrieve_payloads_indexed_len(self, pay_cts, all_payloads_count: int, layout: "PayloadLayout", seed: bytes,
+                                      indices, bits: int = 0) -> np.ndarray:
+        """omr_auditor_retrieve_payloads_indexed_len: u16 [len(indices)][layout.payload_len], the right-hand side
+        gathered across the stripes and the solve on the device."""
+        c = self._cts(pay_cts, bits)
+        idx = np.ascontiguousarray(sorted(indices), dtype=np.uintp)
+        out = np.zeros((len(idx), layout.payload_len if layout else 0), np.uint16)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_auditor_retrieve_payloads_indexed_len(self._h, c.ctypes.data, c.shape[0], bits,
+                                                               all_payloads_count, _layout_ref(layout), ptr,
+                                                               idx.ctypes.data, len(idx), out.ctypes.data),
+               "omr_auditor_retrieve_payloads_indexed_len")
+        return out
+
     def retrieve_payloads_seek(self, pay_cts, all_payloads_count: int, combination_count: int, seed: bytes, indices,
                                seek: "WeightSeek" = None, bits: int = 0) -> np.ndarray:
         """omr_auditor_retrieve_payloads_seek: the same with the reference's weights found through the seek
@@ -1604,6 +1685,33 @@ class Detector:
                                                         per_ct, d_out or None, stream or None),
                "omr_encode_payloads_indexed_device")
 
+    def encode_pertinent_payloads_indexed_len(self, pertinency_vector, payloads, seed: bytes, all_payloads_count: int,
+                                              combination_count: int, per_ct: int, first_ct: int, n_ct: int,
+                                              global_offset: int = 0, payload_len: int = None) -> np.ndarray:
+        """omr_encode_payloads_indexed_len: payloads u16 [D][payload_len] (default: the array's width), the
+        ciphertexts [first_ct, first_ct + n_ct) of the length's layout at per_ct combinations per group."""
+        pv = np.ascontiguousarray(pertinency_vector, dtype=np.uint64)
+        pay = np.ascontiguousarray(payloads, dtype=np.uint16)
+        L = pay.shape[1] if payload_len is None else payload_len
+        out = np.empty((min(max(n_ct, 0), 65535), 2, N2), np.uint64)
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_encode_payloads_indexed_len(self._h, pv.ctypes.data, pay.ctypes.data, pv.shape[0],
+                                                     global_offset, all_payloads_count, ptr, combination_count, L,
+                                                     per_ct, first_ct, n_ct, out.ctypes.data),
+               "omr_encode_payloads_indexed_len")
+        return out
+
+    def encode_pertinent_payloads_indexed_len_device(self, d_pv: int, d_payloads: int, D: int, global_offset: int,
+                                                     all_payloads_count: int, seed: bytes, combination_count: int,
+                                                     payload_len: int, per_ct: int, first_ct: int, n_ct: int,
+                                                     d_out: int, stream: int = 0) -> None:
+        ptr, _keep = _seed_ptr(seed)
+        _check(lib().omr_encode_payloads_indexed_len_device(self._h, d_pv or None, d_payloads or None, D,
+                                                            global_offset, all_payloads_count, ptr, combination_count,
+                                                            payload_len, per_ct, first_ct, n_ct, d_out or None,
+                                                            stream or None),
+               "omr_encode_payloads_indexed_len_device")
+
     def encode_pertinent_payloads_seek(self, pertinency_vector, payloads, seed: bytes, seek: "WeightSeek",
                                        rp: RetrievalParams, global_offset: int = 0, first_ct: int = 0,
                                        n_ct: int = None) -> np.ndarray:
@@ -1650,12 +1758,15 @@ class Detector:
         _check(lib().omr_ctx_set_compact_staging(self._h, max_ciphertexts), "omr_ctx_set_compact_staging")
 
     def digest_session(self, all_payloads_count: int, pertinent_count: int, index_seed: int, weight_seed: bytes,
-                       stream: int = 0, indexed: bool = False, seek: bool = False) -> "DigestSession":
+                       stream: int = 0, indexed: bool = False, seek: bool = False,
+                       payload_len: int = None) -> "DigestSession":
         """A digest session on this detector (omr_digest_begin): detect + encode a board piece by
         piece without holding its pertinency vector. A context manager. indexed=True: a session with
         indexed payload weights (omr_digest_begin_indexed), which holds no weight table. seek=True: the
-        reference's weights without the table (omr_digest_begin_seek): the digest of the default session."""
-        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream, indexed, seek)
+        reference's weights without the table (omr_digest_begin_seek): the digest of the default session.
+        payload_len=L (with indexed=True): a board whose payloads are L words long (omr_digest_begin_indexed_len)."""
+        return DigestSession(self, all_payloads_count, pertinent_count, index_seed, weight_seed, stream, indexed, seek,
+                             payload_len)
 
     # ---- stage entry points (benches/two_level_bs.rs) ----
     def first_level(self, clue_a, clue_b) -> np.ndarray:
@@ -1735,18 +1846,26 @@ class DigestSession:
     device and at most one detect chunk of pertinency ciphertexts is ever allocated."""
 
     def __init__(self, detector: "Detector", all_payloads_count: int, pertinent_count: int, index_seed: int,
-                 weight_seed: bytes, stream: int = 0, indexed: bool = False, seek: bool = False):
+                 weight_seed: bytes, stream: int = 0, indexed: bool = False, seek: bool = False,
+                 payload_len: int = None):
         seed = np.frombuffer(bytes(weight_seed), dtype=np.uint8).copy()
         if seed.size != 32:
             raise OmrError("weight_seed must be 32 bytes")
         h = C.c_void_p()
         if indexed and seek:
             raise OmrError("a session uses indexed weights or the reference's weights by seek, not both")
+        if payload_len is not None and not indexed:
+            raise OmrError("a payload length of its own needs indexed weights")
         begin, what = ((lib().omr_digest_begin_indexed, "omr_digest_begin_indexed") if indexed else
                        (lib().omr_digest_begin_seek, "omr_digest_begin_seek") if seek else
                        (lib().omr_digest_begin, "omr_digest_begin"))
-        _check(begin(detector.handle, all_payloads_count, pertinent_count, index_seed, seed.ctypes.data,
-                     stream or None, C.byref(h)), what)
+        if payload_len is not None:
+            _check(lib().omr_digest_begin_indexed_len(detector.handle, all_payloads_count, pertinent_count, index_seed,
+                                                      seed.ctypes.data, payload_len, stream or None, C.byref(h)),
+                   "omr_digest_begin_indexed_len")
+        else:
+            _check(begin(detector.handle, all_payloads_count, pertinent_count, index_seed, seed.ctypes.data,
+                         stream or None, C.byref(h)), what)
         self._h = h
         self._destroy = lib().omr_digest_destroy
         self._detector = detector  # the context outlives the session
@@ -1754,21 +1873,23 @@ class DigestSession:
             detector._sessions = weakref.WeakSet()
         detector._sessions.add(self)
         self._info = self.info()
+        self._len = self.payload_layout().payload_len
 
     def update(self, clue_a, clue_b, payloads, global_offset: int = 0) -> None:
-        """Host arrays u16 [D][512], [D][7], [D][612] for global indices global_offset..+D; returns
-        when the device has finished with them."""
+        """Host arrays u16 [D][512], [D][7], [D][payload_len] (612 unless the session was begun with a
+        payload_len of its own) for global indices global_offset..+D; returns when the device has finished
+        with them."""
         a = np.ascontiguousarray(clue_a, dtype=np.uint16)
         b = np.ascontiguousarray(clue_b, dtype=np.uint16)
         p = np.ascontiguousarray(payloads, dtype=np.uint16)
         D = a.shape[0]
-        if a.shape != (D, N0) or b.shape != (D, CLUE_COUNT) or p.shape != (D, PAYLOAD_LENGTH):
-            raise OmrError("clues must be u16 [D][512] and [D][7], payloads u16 [D][612]")
+        if a.shape != (D, N0) or b.shape != (D, CLUE_COUNT) or p.shape != (D, self._len):
+            raise OmrError(f"clues must be u16 [D][512] and [D][7], payloads u16 [D][{self._len}]")
         _check(lib().omr_digest_update(self._h, a.reshape(-1), b.reshape(-1), p.reshape(-1), D, global_offset),
                "omr_digest_update")
 
     def update_device(self, d_clue_a: int, d_clue_b: int, d_payloads: int, D: int, global_offset: int = 0) -> None:
-        """Device pointers (same layouts); enqueued on the session's stream, the caller keeps the
+        """Device pointers (same layouts, the payloads [D][payload_len] of the session); enqueued on the session's stream, the caller keeps the
         buffers alive until read() or Detector.check()."""
         _check(lib().omr_digest_update_device(self._h, d_clue_a, d_clue_b, d_payloads, D, global_offset),
                "omr_digest_update_device")
@@ -1823,6 +1944,12 @@ class DigestSession:
         t = _DigestInfo()
         _check(lib().omr_digest_get_info(self._h, C.byref(t)), "omr_digest_get_info")
         return {n: getattr(t, n) for n, _ in _DigestInfo._fields_}
+
+    def payload_layout(self) -> "PayloadLayout":
+        """omr_digest_get_payload_layout: the layout of the session's payload digest."""
+        t = _PayloadLayout()
+        _check(lib().omr_digest_get_payload_layout(self._h, C.byref(t)), "omr_digest_get_payload_layout")
+        return PayloadLayout(**{n: getattr(t, n) for n, _ in _PayloadLayout._fields_})
 
     def device_bytes(self) -> dict:
         """omr_digest_device_bytes: the device memory the session owns now, and the weights' share of it."""
